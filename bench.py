@@ -11,11 +11,16 @@ per GPU, each hashing its own 1024 chunks (weak scaling, per-GPU work queues, no
 collective); a barrier + synchronize brackets the timed steps and the time is the max over
 ranks (one all_reduce of a scalar, timing only).
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) sets up, warms up, times the N steps, writes
+the last step's outputs with --dump-outputs DIR, and prints the result line.  --full adds, after
+the headline, everything else this file measures or checks: the engine clock over the timed region,
+the per-rank spot checks, the side legs (--*-leg) and the CPU baselines.
+
 Printed on rank 0: ONE JSON line with the driver's keys plus
   roofline     -- the hashing kernel's algorithmic bytes per launch / its average launch time
                   (HIP events on the launch stream), against the 8 TB/s HBM3E peak; traffic
                   from profiles/<round>_traffic.json (rocprofv3 FETCH_SIZE pass) when present;
-  cpu_baseline -- the C restatement of the reference (oracle/, kind "port") over the same
+  cpu_baseline -- (--full) the C restatement of the reference (oracle/, kind "port") over the same
                   bytes on the host cores, N=1 rank 0 only, digests checked against the GPU's.
 """
 from __future__ import annotations
@@ -51,8 +56,17 @@ def kernel_names() -> dict:
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--steps", type=int, default=20,
+                   help="timed steps of the headline (a workload of several launches per pass, --workload ingest "
+                        "or mixed with --mixed-launches, times one pass: one step per launch)")
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every side leg, CPU baseline and check (the --*-leg options "
+                        "choose among them), measure the engine clock and spot-check the digests; without it a "
+                        "run sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (per-job Sums, CRC-32 and "
+                        "status) as DIR/<name>.npy")
     p.add_argument("--chunks", type=int, default=1024, help="chunks per GPU")
     p.add_argument("--chunk-bytes", type=int, default=4 << 20)
     p.add_argument("--mode", choices=["auto", "deep", "wide", "plan", "group4", "group8", "group16", "group32", "fed4",
@@ -122,7 +136,11 @@ def parse_args(argv=None):
     p.add_argument("--watchdog", type=float, default=0.0,
                    help="dump every thread's Python stack to stderr after this many seconds (faulthandler; "
                         "0 = off; the GPU test of this file arms it)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.workload == "uploads" and (args.full or args.dump_outputs):
+        # the uploads workload is tools/bench_uploads alone: no timed steps of this file, no side legs
+        p.error("--workload uploads runs the native upload harness alone: --full and --dump-outputs do not apply")
+    return args
 
 
 class Legs:
@@ -760,10 +778,12 @@ def binding_roofline(kernel: str, achieved_gbs: float, concurrent_msgs: int, sha
     return out
 
 
-def run_timed(batches, steps: int, warmup: int, mode: int, device: str, stream, dist, progress: bool = False):
+def run_timed(batches, steps: int, warmup: int, mode: int, device: str, stream, dist, progress: bool = False,
+              meter: bool = True):
     """W untimed warm-up launches, then exactly `steps` launches bracketed by barrier +
     synchronize; returns (wall seconds of this rank, average kernel ms from HIP events recorded
-    on the launch stream, the effective engine clock over the timed launches (ClockMeter))."""
+    on the launch stream, the effective engine clock over the timed launches (ClockMeter; None
+    without `meter`))."""
     import torch
 
     for _ in range(warmup):
@@ -775,8 +795,9 @@ def run_timed(batches, steps: int, warmup: int, mode: int, device: str, stream, 
     if dist:
         dist.barrier()
     torch.cuda.synchronize(device)
-    clk = clock_meter(torch.device(device).index or 0)
-    clk.start(stream.cuda_stream)
+    clk = clock_meter(torch.device(device).index or 0) if meter else None
+    if clk:
+        clk.start(stream.cuda_stream)
     t0 = time.perf_counter()
     ev0.record(stream)
     for k in range(steps):
@@ -786,12 +807,13 @@ def run_timed(batches, steps: int, warmup: int, mode: int, device: str, stream, 
             print(f"[bench] step {k + 1}/{steps} done at {time.perf_counter() - t0:.1f} s", file=sys.stderr,
                   flush=True)
     ev1.record(stream)
-    clk.end(stream.cuda_stream)
+    if clk:
+        clk.end(stream.cuda_stream)
     torch.cuda.synchronize(device)
     if dist:
         dist.barrier()
     wall = time.perf_counter() - t0
-    clock = clk.stop()
+    clock = clk.stop() if clk else None
     for b in batches:
         assert (b.status_host() == 0).all(), "hash jobs reported an error status"
     return wall, ev0.elapsed_time(ev1) / max(1, steps), clock
@@ -1101,6 +1123,28 @@ def span_crc_leg(args, ctx, device: str, stream, gib: int = 16, reps: int = 5):
             "crc_matches_zlib": ok, "clock": clock, "note": "HIP events on the launch stream; not `value`"}
 
 
+DUMP_MAX_JOBS = 262144  # 24 B of Sum per job as float32: 24 MiB; a larger batch is sampled (seeded)
+
+
+def dump_outputs(out_dir: str, batch, rank: int = 0) -> None:
+    """--dump-outputs: what the caller of the last timed step holds afterwards, one row per job, as
+    DIR/<name>.npy (rank 0; other ranks DIR/<name>.rank<r>.npy): `sums` (n x 24 float32: the 20 SHA-1
+    digest bytes, then the 4 CRC-32 bytes, of each job's Sum), `crc32` (n float64: the CRC-32 states)
+    and `status` (n float32).  The inputs are seeded, so two builds' files compare entry for entry.
+    A batch of more than DUMP_MAX_JOBS jobs is sampled by a fixed seed (`jobs`: the rows kept)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"sums": batch.sums_host().astype(np.float32), "crc32": batch.crc_sum().astype(np.float64),
+              "status": batch.status_host().astype(np.float32)}
+    if batch.n > DUMP_MAX_JOBS:
+        keep = np.sort(np.random.default_rng(0xEFE5).choice(batch.n, DUMP_MAX_JOBS, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["jobs"] = keep.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.watchdog > 0:
@@ -1153,8 +1197,11 @@ def main(argv=None):
             for b in batches:
                 b.make_plan()  # host-side planning stays outside the timed region
         steps = args.steps if len(batches) == 1 else len(batches)
-        wall, kernel_ms, clock = run_timed(batches, steps, args.warmup, mode, device, stream, dist, args.progress)
+        wall, kernel_ms, clock = run_timed(batches, steps, args.warmup, mode, device, stream, dist, args.progress,
+                                           meter=args.full)
     print(f"[bench] headline: {steps} steps in {wall:.3f} s on this rank", file=sys.stderr, flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batches[(steps - 1) % len(batches)], rank)
     rank_wall = wall
     wall = max_over_ranks(wall, device if args.dist_backend == "nccl" else None)  # slowest rank
 
@@ -1210,16 +1257,20 @@ def main(argv=None):
     # Which device each rank ran on, its own rate and kernel time, and spot checks of its digests
     # (SURVEY.md §8(e)): a weak-scaling line must show N distinct GPUs doing the work.  After the timed
     # region; one all_gather_object of a small dict, measurement only.
+    # A plain one-GPU run (no --full) stops at its headline and leaves the records out.
     from efes_amd.shard import gather_rank_records, summarize_ranks
 
-    rec = {"rank": rank, "local_rank": local, "device": dev_index, "bdf": device_bdf(dev_index),
-           "GiB/s": round(bytes_timed / rank_wall / GiB, 3), "wall_s": round(rank_wall, 4),
-           "kernel_ms": round(kernel_ms, 4), "clock_mhz": clock.get("mhz"),
-           "spot_check": rank_spot_check(args, data, batches, config)}
-    records = gather_rank_records(rec)
-    out["ranks"] = records
-    out["ranks_check"] = summarize_ranks(records, world, args.all_ranks_on_device0)
-    if args.workload == "chunks4m":
+    ranks_ok = True
+    if args.full or world > 1:
+        rec = {"rank": rank, "local_rank": local, "device": dev_index, "bdf": device_bdf(dev_index),
+               "GiB/s": round(bytes_timed / rank_wall / GiB, 3), "wall_s": round(rank_wall, 4),
+               "kernel_ms": round(kernel_ms, 4), "clock_mhz": (clock or {}).get("mhz"),
+               "spot_check": rank_spot_check(args, data, batches, config)}
+        records = gather_rank_records(rec)
+        out["ranks"] = records
+        out["ranks_check"] = summarize_ranks(records, world, args.all_ranks_on_device0)
+        ranks_ok = out["ranks_check"]["ok"]
+    if args.full and args.workload == "chunks4m":
         n, chunk = args.chunks, args.chunk_bytes
         if args.host_inclusive == "on" or (args.host_inclusive == "auto" and world == 1):
             out["host_inclusive"] = legs.run("host_inclusive", host_inclusive, ctx, data, n, chunk, not args.sha1_only,
@@ -1260,7 +1311,7 @@ def main(argv=None):
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
-    if not out["ranks_check"]["ok"]:
+    if not ranks_ok:
         # after the line is out: the driver keeps the measurement, and the run still fails loudly
         print(f"bench.py: rank check failed: {out['ranks_check']}", file=sys.stderr, flush=True)
         sys.exit(3)

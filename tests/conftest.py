@@ -31,4 +31,8 @@ def efes_lib():
     from efes_amd import build
     build.build_lib()
     from efes_amd import _lib
+    # Load through the binding before any test opens LIB_PATH itself: lib() imports torch first, so the
+    # process keeps ONE HIP runtime (_lib._bind_process_hip_runtime) and the GPU tests that follow in
+    # the same pytest process still find the device.
+    _lib.lib()
     return _lib

@@ -284,15 +284,23 @@ def test_integration_doc_two_build_targets():
     # the reason, measured: one stream on the GPU vs one core
     assert "0.085 GiB/s" in sec and "0.53–0.60 GiB/s" in sec
     assert "No binary routes between the two" in sec
-    # the reference lines cited are the ones that build with CGO_ENABLED=0
-    ref = "/root/reference"
-    if os.path.isdir(ref):
-        assert "CGO_ENABLED=0 go build" in open(os.path.join(ref, "Makefile")).read().split("\n")[5]
-        assert "CGO_ENABLED=0" in open(os.path.join(ref, ".goreleaser.yml")).read().split("\n")[8]
+    # the reference lines cited are the ones that build with CGO_ENABLED=0 (their line numbers are
+    # recorded in tests/golden/reference_names.json)
+    lines = _reference_names()["build_lines"]
+    for name in ("Makefile", ".goreleaser.yml"):
+        cited = {int(x) for x in re.findall(rf"`{re.escape(name)}:(\d+)`", sec)}
+        assert cited and cited <= set(lines[name]), (name, cited, lines[name])
 
 
 # ---- the Go binding, go/*.go (no Go toolchain here: its ownership rules, checked as text) -----------
-REF = "/root/reference"
+def _reference_names() -> dict:
+    """What the reference's Go files define and use, names only (tests/golden/make_reference_names.py)."""
+    import json
+
+    with open(os.path.join(ROOT, "tests", "golden", "reference_names.json")) as f:
+        return json.load(f)
+
+
 DIGEST_FILES = ("sha1.go", "sha1_efes.go", "crc32.go", "crc32_efes.go")  # replaced under -tags efesgpu
 GO_DIR = os.path.join(ROOT, "go")
 
@@ -375,36 +383,31 @@ def test_go_binding_replaces_the_digest_files_whole():
     _efes.go files read Go struct fields and define MarshalText/UnmarshalText, so they cannot
     compile beside it): every method the four define on sha1digest / crc32digest is defined by the
     binding, no other reference file defines one, and every package-level name of the four that
-    another reference file uses is defined by the binding.  Needs the reference (skipped without)."""
+    another reference file uses is defined by the binding.  The reference's side -- the names its files
+    define and use -- is recorded in tests/golden/reference_names.json."""
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for f in DIGEST_FILES:
         assert f"`{f}`" in doc[doc.index("## 1. Build"):doc.index("## 3.")], f
-    if not os.path.isdir(REF):
-        pytest.skip("reference not present")
+    names = _reference_names()
+    assert sorted(names["digest_files"]) == sorted(DIGEST_FILES)
     binding = "\n".join(_go_sources().values())
     mine = {(t, n) for r, t, n, _ in _go_funcs(binding) if r}
     mine_top = {n for r, _t, n, _ in _go_funcs(binding) if not r} | set(re.findall(r"^var (\w+)", binding, flags=re.M)) \
         | set(re.findall(r"^type (\w+)", binding, flags=re.M))
     theirs, defined = set(), set()
     for f in DIGEST_FILES:
-        src = open(os.path.join(REF, f)).read()
-        theirs |= {(t, n) for r, t, n, _ in _go_funcs(src) if r}
-        defined |= {n for r, _t, n, _ in _go_funcs(src) if not r}
-        defined |= set(re.findall(r"^(?:var|const|type) (\w+)", src, flags=re.M))
-        for blk in re.findall(r"^(?:var|const) \((.*?)^\)", src, flags=re.M | re.S):
-            defined |= set(re.findall(r"^\s+(\w+)", blk, flags=re.M))
+        theirs |= {tuple(m) for m in names["digest_files"][f]["methods"]}
+        defined |= set(names["digest_files"][f]["defined"])
     # the exported method sets (hash.Hash, encoding.TextMarshaler/TextUnmarshaler, Sum32); sha1.go's
     # unexported checkSum is its own Sum's helper and no other file calls a digest's unexported method
-    assert {m for m in theirs if m[0] in ("sha1digest", "crc32digest") and m[1][0].isupper()} <= mine
-    for f in sorted(os.listdir(REF)):
-        if not f.endswith(".go") or f in DIGEST_FILES:
-            continue
-        src = open(os.path.join(REF, f)).read()
-        src = re.sub(r'//.*$|"(?:\\.|[^"\\])*"|`[^`]*`', "", src, flags=re.M)  # code only
-        others = {(t, n) for r, t, n, _ in _go_funcs(src) if r and t in ("sha1digest", "crc32digest")}
-        assert not others, (f, others)
-        used = {n for n in defined if re.search(rf"(?<![.\w]){n}\b", src)}
-        assert used <= mine_top, (f, used - mine_top)
+    exported = {m for m in theirs if m[0] in ("sha1digest", "crc32digest") and m[1][0].isupper()}
+    assert len(exported) >= 10 and exported <= mine, exported - mine
+    assert len(names["other_files"]) >= 10
+    for f, rec in sorted(names["other_files"].items()):
+        assert f.endswith(".go") and f not in DIGEST_FILES
+        assert not rec["digest_methods"], (f, rec["digest_methods"])
+        used = set(rec["uses"])
+        assert used <= defined and used <= mine_top, (f, used - mine_top)
 
 
 def test_library_env_vars_are_the_documented_four():
@@ -460,7 +463,8 @@ def test_go_files_are_the_tagged_drop_in():
 def test_build_tag_patch_applies_to_the_reference(tmp_path):
     """go/efesgpu_build_tags.patch puts `//go:build !efesgpu` and a blank line above line 1 of exactly the
     four digest files (sha1.go:1, sha1_efes.go:1, crc32.go:1, crc32_efes.go:1) and nothing else;
-    `patch --dry-run`, then the real apply, on a copy of the four reference files."""
+    `patch --dry-run`, then the real apply, on stand-ins for the four reference files: the hunks carry
+    no context lines, so they apply to any text, and each stand-in opens the way a Go file does."""
     import shutil
 
     pt = os.path.join(GO_DIR, "efesgpu_build_tags.patch")
@@ -472,17 +476,18 @@ def test_build_tag_patch_applies_to_the_reference(tmp_path):
     assert not re.findall(r"^-(?!-- )", text, flags=re.M)  # removes nothing
     if not shutil.which("patch"):
         pytest.skip("patch(1) not installed")
-    if not os.path.isdir(REF):
-        pytest.skip("reference not present")
+    assert not re.findall(r"^ ", text, flags=re.M)  # no context lines either
+    before = {f: f"// {f}: a stand-in with the reference file's name\npackage main\n\nvar standIn{i} = {i}\n"
+              for i, f in enumerate(DIGEST_FILES)}
     for f in DIGEST_FILES:
-        shutil.copy(os.path.join(REF, f), tmp_path / f)
+        (tmp_path / f).write_text(before[f])
     r = subprocess.run(["patch", "-p1", "--dry-run", "-i", pt], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     r = subprocess.run(["patch", "-p1", "-i", pt], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     for f in DIGEST_FILES:
         got = (tmp_path / f).read_text()
-        assert got == "//go:build !efesgpu\n\n" + open(os.path.join(REF, f)).read(), f
+        assert got == "//go:build !efesgpu\n\n" + before[f], f
 
 
 def test_go_pool_opens_every_device_and_skips_failures():

@@ -810,7 +810,7 @@ def test_bench_emits_driver_json(env):
     # drain_path 15.6 s of it, CPU-bound harnesses); their shortest points keep each leg exercised
     CHILD_S, WATCHDOG_S = 108, 95
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "-X", "faulthandler", os.path.join(root, "bench.py"), "--chunks", "16",
+    cmd = [sys.executable, "-X", "faulthandler", os.path.join(root, "bench.py"), "--full", "--chunks", "16",
            "--chunk-bytes", "65536", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.1", "--segment-bytes", "16384",
            "--mixed-leg", "off", "--uploads-leg", "off", "--latency-uploads", "1,16", "--drain-workers", "1,64",
            "--watchdog", str(WATCHDOG_S)]
@@ -834,6 +834,49 @@ def test_bench_emits_driver_json(env):
     assert d["cpu_baseline"]["digests_match_gpu"] and d["host_inclusive"]["digests_match_device_path"]
     kernels = [p["kernel"] for p in d["concurrency"]["points"]]
     assert kernels[:2] == ["deep_kernel", "fed_kernel<4, 2>"] and kernels[-1] == "wide_kernel"
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(env, oracle, tmp_path):
+    """Without --full bench.py stops at its headline: the result line carries the driver's keys and
+    none of the side legs, --steps sets the timed steps, and --dump-outputs writes the last step's
+    Sums, CRC-32s and status as float arrays equal to hashlib/zlib over the same seeded bytes."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, chunk = 16, 65536
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--chunks", str(n), "--chunk-bytes", str(chunk), "--dump-outputs", str(tmp_path / "out"), "--progress"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=100)
+    assert r.returncode == 0, r.stderr[-8000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    # three launches were timed, not merely reported: --progress logs each timed step as it completes,
+    # and the wall time per step covers the launches' own time on the device (HIP events, same region)
+    import re
+    assert re.findall(r"\[bench\] step (\d+)/3 done", r.stderr) == ["1", "2", "3"], r.stderr[-2000:]
+    assert d["ms_per_step"] >= 0.9 * d["roofline"]["kernel_ms"] > 0
+    assert d["value"] == pytest.approx(3 * n * chunk / (d["ms_per_step"] * 3e-3) / (1 << 30), rel=1e-2)
+    assert d["cpu_baseline"] is None and d["leg_seconds"] == {}
+    for leg in ("host_inclusive", "sha1_only_config", "span_crc", "ingest_config", "uploads_path", "go_surface_path",
+                "patch_latency", "receiver_path", "drain_path", "concurrency", "mixed_config", "config0_cpu", "ranks"):
+        assert leg not in d, leg
+    assert "[bench]" in r.stderr and ": start at" not in r.stderr  # no leg was started
+    sums, crc, status = (np.load(tmp_path / "out" / f"{name}.npy") for name in ("sums", "crc32", "status"))
+    assert sums.dtype == np.float32 and sums.shape == (n, 24) and crc.dtype == np.float64 and crc.shape == (n,)
+    assert status.dtype == np.float32 and (status == 0).all()
+    host = oracle.fill_synthetic(n * chunk, 0xEFE5).tobytes()
+    for j in range(n):
+        piece = host[j * chunk:(j + 1) * chunk]
+        want = hashlib.sha1(piece).digest() + zlib.crc32(piece).to_bytes(4, "big")
+        assert bytes(sums[j].astype(np.uint8)) == want, j
+        assert int(crc[j]) == zlib.crc32(piece), j
 
 
 def test_streaming_digests_batch_across_threads(env, oracle):

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 out=gpurun_out/${1:-r04_fetch}
 mkdir -p "$out"
 MB=tools/microbench/mb_wide_fetch
-BENCH="python3 bench.py --no-cpu-baseline --host-inclusive off --ingest-leg off --mixed-leg off --concurrency-leg off \
+BENCH="python3 bench.py --full --no-cpu-baseline --host-inclusive off --ingest-leg off --mixed-leg off --concurrency-leg off \
  --uploads-leg off --go-surface-leg off --latency-leg off --receiver-leg off --drain-leg off --span-leg off --sha1-leg off \
  --chunks 196608 --chunk-bytes 1048576 --mode wide --steps 3 --warmup 1"
 timeout -k 10 150 $MB 196608 1048576 0 2 > "$out/timing_pad0.json"

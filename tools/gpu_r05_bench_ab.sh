@@ -7,12 +7,12 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r05_bench_ab}
 mkdir -p "$O"
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
 echo bench ok
 for rep in 1 2; do
   for lib in product pace32 nopace; do
     if [ $lib = product ]; then env_lib=""; else env_lib="EFES_LIB_OVERRIDE=$PWD/efes_amd/lib/ab/libefeshash_$lib.so"; fi
-    timeout -k 10 300 env $env_lib python3 bench.py --workload ingest --no-cpu-baseline > "$O/ab_$lib.$rep.json" 2> "$O/ab_$lib.$rep.err" \
+    timeout -k 10 300 env $env_lib python3 bench.py --full --workload ingest --no-cpu-baseline > "$O/ab_$lib.$rep.json" 2> "$O/ab_$lib.$rep.err" \
       || { echo "ab $lib failed"; tail -5 "$O/ab_$lib.$rep.err"; exit 1; }
     python3 - "$O/ab_$lib.$rep.json" $lib $rep <<'PY' | tee -a "$O/ab.log"
 import json, sys

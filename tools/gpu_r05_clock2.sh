@@ -8,7 +8,7 @@ O=gpurun_out/${1:-r05_clock2}
 mkdir -p "$O"
 B="--no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-surface-leg off --latency-leg off --receiver-leg off --drain-leg off --concurrency-leg off --mixed-leg off"
 for rep in 1 2; do
-  timeout -k 10 300 python3 bench.py $B > "$O/bench.$rep.json" 2> "$O/bench.$rep.err" || { tail -5 "$O/bench.$rep.err"; exit 1; }
+  timeout -k 10 300 python3 bench.py --full $B > "$O/bench.$rep.json" 2> "$O/bench.$rep.err" || { tail -5 "$O/bench.$rep.err"; exit 1; }
   python3 - "$O/bench.$rep.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -18,7 +18,7 @@ for name, leg in (("headline", d), ("ingest", d["ingest_config"]), ("span", d["s
 PY
 done
 timeout -s KILL 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE --output-format csv \
-  -d "$O/pmc" -o run -- python3 bench.py $B --span-leg off > "$O/pmc.log" 2>&1 || { echo "pmc failed"; tail -5 "$O/pmc.log"; exit 1; }
+  -d "$O/pmc" -o run -- python3 bench.py --full $B --span-leg off > "$O/pmc.log" 2>&1 || { echo "pmc failed"; tail -5 "$O/pmc.log"; exit 1; }
 python3 - "$O" <<'PY'
 import csv, collections, statistics, sys
 O = sys.argv[1]

@@ -15,7 +15,7 @@ B="--no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-
  --receiver-leg off --drain-leg off --concurrency-leg off --mixed-leg off --ingest-leg off --span-leg off --steps 5 --warmup 1"
 run() {  # name lib chunks mode
   local env_lib=""; [ "$2" = product ] || env_lib="EFES_LIB_OVERRIDE=$V"
-  timeout -k 10 200 env $env_lib python3 bench.py $B --chunks $3 --mode $4 > "$O/$1.json" 2> "$O/$1.err" || { tail -5 "$O/$1.err"; exit 1; }
+  timeout -k 10 200 env $env_lib python3 bench.py --full $B --chunks $3 --mode $4 > "$O/$1.json" 2> "$O/$1.err" || { tail -5 "$O/$1.err"; exit 1; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['unit'], d['ms_per_step'], 'ms', d.get('clock',{}).get('mhz'))" "$O/$1.json" "$1" | tee -a "$O/ab.log"
 }
 for rep in 1 2; do

@@ -6,10 +6,10 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r05b}
 mkdir -p "$O"
-timeout -k 10 600 python bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
 echo bench ok
 for rep in 1 2; do
-  timeout -k 10 300 python3 bench.py --workload ingest --no-cpu-baseline > "$O/ingest.$rep.json" 2> "$O/ingest.$rep.err" || { tail -5 "$O/ingest.$rep.err"; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --workload ingest --no-cpu-baseline > "$O/ingest.$rep.json" 2> "$O/ingest.$rep.err" || { tail -5 "$O/ingest.$rep.err"; exit 1; }
 done
 python3 - "$O" <<'PY'
 import json, sys

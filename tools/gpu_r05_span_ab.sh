@@ -26,7 +26,7 @@ B="--no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-
 for rep in 1 2; do
   for lib in product "${VARIANTS[@]}"; do
     if [ "$lib" = product ]; then env_lib=""; else env_lib="EFES_LIB_OVERRIDE=$PWD/efes_amd/lib/ab/libefeshash_$lib.so"; fi
-    timeout -k 10 200 env $env_lib python3 bench.py $B > "$O/span_$lib.$rep.json" 2> "$O/span_$lib.$rep.err" || { tail -5 "$O/span_$lib.$rep.err"; exit 1; }
+    timeout -k 10 200 env $env_lib python3 bench.py --full $B > "$O/span_$lib.$rep.json" 2> "$O/span_$lib.$rep.err" || { tail -5 "$O/span_$lib.$rep.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['span_crc']; print(sys.argv[2], sys.argv[3], d['value'], 'GiB/s', d['roofline']['achieved'], 'GB/s', d['roofline']['frac'], d['crc_matches_zlib'], d['clock'].get('mhz'))" "$O/span_$lib.$rep.json" $rep $lib | tee -a "$O/ab.log"
   done
 done

@@ -11,7 +11,7 @@ B="--no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-
 for rep in 1 2; do
   for lib in product "$@"; do
     env_lib=""; [ "$lib" = product ] || env_lib="EFES_LIB_OVERRIDE=$PWD/efes_amd/lib/ab/libefeshash_$lib.so"
-    timeout -k 10 300 env $env_lib python3 bench.py $B > "$O/$lib.$rep.json" 2> "$O/$lib.$rep.err" || { tail -5 "$O/$lib.$rep.err"; exit 1; }
+    timeout -k 10 300 env $env_lib python3 bench.py --full $B > "$O/$lib.$rep.json" 2> "$O/$lib.$rep.err" || { tail -5 "$O/$lib.$rep.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); s=d['span_crc']; m=d['mixed_config']; print(sys.argv[2], sys.argv[3], 'span', s['value'], 'GiB/s', s['roofline']['achieved'], 'GB/s', s['clock'].get('mhz'), 'MHz', s['crc_matches_zlib'], '| mixed', m['value'])" "$O/$lib.$rep.json" $rep $lib | tee -a "$O/ab.log"
   done
 done

@@ -18,10 +18,10 @@ print(f"span {d['value']} GiB/s  probe {c.get('probe_mhz')} MHz ({c.get('probe_c
       f"smi mean {c.get('smi_mhz_mean')} (n={c.get('smi_samples')})")
 PY
 }
-timeout -k 10 200 python3 bench.py $B > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 200 python3 bench.py --full $B > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
 show "$O/bench.json"
 timeout -s KILL 200 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d "$O/pmc" -o run -- \
-  python3 bench.py $B > "$O/pmc_bench.json" 2> "$O/pmc.err" || { echo "pmc failed"; tail -5 "$O/pmc.err"; exit 1; }
+  python3 bench.py --full $B > "$O/pmc_bench.json" 2> "$O/pmc.err" || { echo "pmc failed"; tail -5 "$O/pmc.err"; exit 1; }
 show "$O/pmc_bench.json"
 python3 - "$O" <<'PY'
 import csv, collections, sys

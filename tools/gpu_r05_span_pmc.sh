@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r05_span_pmc}
 mkdir -p "$O"
-B="python3 bench.py --no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-surface-leg off \
+B="python3 bench.py --full --no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-surface-leg off \
  --latency-leg off --receiver-leg off --drain-leg off --concurrency-leg off --mixed-leg off --ingest-leg off --steps 2 --warmup 1"
 i=0
 for set in "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" \

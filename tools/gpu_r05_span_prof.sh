@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:?}"
 export TMPDIR=/tmp
 out=gpurun_out/${1:-r05_span_prof}
 mkdir -p "$out"
-BENCH="python3 bench.py --no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-surface-leg off \
+BENCH="python3 bench.py --full --no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-surface-leg off \
  --latency-leg off --receiver-leg off --drain-leg off --concurrency-leg off --mixed-leg off --ingest-leg off --steps 2 --warmup 1"
 summ() {  # $1 = run dir: median of every counter per kernel
   python3 - "$1" <<'PY'

@@ -16,7 +16,7 @@ B="--no-cpu-baseline --host-inclusive off --sha1-leg off --uploads-leg off --go-
 for rep in 1 2 3; do
   for lib in product $VAR; do
     env_lib=""; [ $lib = product ] || env_lib="EFES_LIB_OVERRIDE=$V"
-    timeout -k 10 300 env $env_lib python3 bench.py $B > "$O/$lib.$rep.json" 2> "$O/$lib.$rep.err" || { tail -5 "$O/$lib.$rep.err"; exit 1; }
+    timeout -k 10 300 env $env_lib python3 bench.py --full $B > "$O/$lib.$rep.json" 2> "$O/$lib.$rep.err" || { tail -5 "$O/$lib.$rep.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['ingest_config']; b=d['binding_roofline']; print(sys.argv[2], sys.argv[3], d['value'], d['roofline']['kernel_ms'], 'ms', b['frac'], b['frac_at_clock'], b['clock_mhz'], d['digests_spot_check'])" "$O/$lib.$rep.json" $rep $lib | tee -a "$O/ab.log"
   done
 done

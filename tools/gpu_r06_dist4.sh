@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out/${1:-r06_dist4}
 mkdir -p "$O"
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29541 \
-  bench.py --gpus 4 --steps 5 --warmup 1 --dist-backend gloo --all-ranks-on-device0 --ingest-scale 0.05 \
+  bench.py --full --gpus 4 --steps 5 --warmup 1 --dist-backend gloo --all-ranks-on-device0 --ingest-scale 0.05 \
   > "$O/dist4.json" 2> "$O/dist4.err" || { echo "dist4 failed"; tail -20 "$O/dist4.err"; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$O/dist4.json').read().strip().splitlines()[-1])
