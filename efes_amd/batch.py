@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, default_context
+from .hashing import Context, crc32_batch_scratch, default_context
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -75,6 +75,8 @@ class DeviceBatch:
         lengths = np.asarray(lengths, dtype=np.uint64)
         n = self.n = int(offsets.size)
         assert lengths.size == n
+        self.has_sha1 = bool(sha1)
+        self._crc_scratch = None  # submit_crc_batch()'s device scratch, allocated once
         self.init_states = fresh_states(n) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
         self.init_crcs = np.zeros(n, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
         self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
@@ -135,16 +137,36 @@ class DeviceBatch:
     def submit(self, mode: int = MODE_AUTO) -> None:
         """Enqueue all jobs, ordered after the work on torch's current stream (data writes,
         reset()) and before the work queued there afterwards (result copies)."""
+        self._ordered(lambda stream: self._launch(mode, stream))
+
+    def _ordered(self, launch) -> None:
+        """launch(stream handle), ordered with torch's current stream as submit() documents."""
         cur = self.torch.cuda.current_stream(self.device)
         if cur.cuda_stream:
-            self._launch(mode, cur.cuda_stream)
+            launch(cur.cuda_stream)
             return
         # Null stream: the library launches on the context's non-blocking stream, which the
         # null stream does not order against; join the two both ways with events.
         ctx_stream = self.torch.cuda.ExternalStream(self.ctx.stream, device=self.device)
         ctx_stream.wait_stream(cur)
-        self._launch(mode, ctx_stream.cuda_stream)
+        launch(ctx_stream.cuda_stream)
         cur.wait_stream(ctx_stream)
+
+    def submit_crc_batch(self) -> None:
+        """The jobs of a batch built with sha1=False through efes_crc32_batch (every job's bytes dealt
+        to the whole GPU in tiles) instead of the job kernels; ordered exactly like submit().  The
+        scratch tensor is allocated on first use and kept: one batch's launches run in stream order."""
+        if self.has_sha1:
+            raise ValueError("submit_crc_batch: the batch carries SHA-1 states (build it with sha1=False)")
+        if self._crc_scratch is None:
+            self._crc_scratch = self.torch.empty(max(crc32_batch_scratch(self.n), 16), dtype=self.torch.uint8,
+                                                 device=self.device)
+        self._ordered(lambda stream: self.ctx.crc32_batch(self.jobs.data_ptr(), self.n, self._crc_scratch.data_ptr(),
+                                                          self._crc_scratch.numel(), stream))
+
+    def run_crc_batch(self) -> None:
+        self.submit_crc_batch()
+        self.torch.cuda.synchronize(self.device)
 
     def _launch(self, mode: int, stream: int) -> None:
         if mode == MODE_PLAN:

@@ -227,6 +227,14 @@ int efes_ctx_create(int device, efes_ctx** out) {
     if (e == hipSuccess) e = hipMemcpy(ctx->d_span, span, sizeof(efes::SpanTables), hipMemcpyHostToDevice);
     free(span);
   }
+  if (e == hipSuccess) {
+    efes::BatchTables* batch = static_cast<efes::BatchTables*>(malloc(sizeof(efes::BatchTables)));
+    if (!batch) e = hipErrorOutOfMemory;
+    if (batch) efes::build_batch_tables(batch);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ctx->d_batch), sizeof(efes::BatchTables));
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_batch, batch, sizeof(efes::BatchTables), hipMemcpyHostToDevice);
+    free(batch);
+  }
   if (e != hipSuccess) {
     efes_ctx_destroy(ctx);
     return EFES_ERR_HIP;
@@ -246,6 +254,7 @@ void efes_ctx_destroy(efes_ctx* ctx) {
     if (ctx->copy) (void)hipStreamSynchronize(ctx->copy);
     if (ctx->d_tabs) (void)hipFree(ctx->d_tabs);
     if (ctx->d_span) (void)hipFree(ctx->d_span);
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     for (hipEvent_t ev : ctx->ev_join)
       if (ev) (void)hipEventDestroy(ev);
@@ -342,6 +351,18 @@ int efes_crc32_span(efes_ctx* ctx, const void* data, uint64_t length, efes_crc32
   if (!ctx || !crc || (!data && length) || (reinterpret_cast<uintptr_t>(crc) & 3)) return EFES_ERR_ARG;
   DeviceGuard g(ctx->device);
   return hip_err(efes::launch_crc_span(data, length, &crc->crc, ctx->d_tabs, ctx->d_span, ctx->cus, pick(ctx, stream)));
+}
+
+size_t efes_crc32_batch_scratch(uint32_t njobs) { return efes::crc_batch_scratch_bytes(njobs); }
+
+int efes_crc32_batch(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* scratch, size_t scratch_bytes,
+                     void* stream) {
+  if (!ctx || (!jobs && njobs) || njobs > EFES_CRC_BATCH_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::crc_batch_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_crc_batch(jobs, njobs, scratch, ctx->d_tabs, ctx->d_batch, ctx->cus, pick(ctx, stream)));
 }
 
 int efes_crc32_tables(uint32_t* out, size_t nwords) {

@@ -1,0 +1,454 @@
+// efes_crc_batch.hip -- CRC-32/IEEE of MANY device buffers in one call, each spread over the whole GPU
+// (efes_crc32_batch, ABI 8).
+//
+// CRC-only jobs of efes_hash_submit run in the SHA-1-shaped kernels, one wavefront per job at best,
+// although CRC-32 is GF(2)-linear and needs no chain (efes_crc_span.hip has the identities).  Here
+// the jobs' bytes are cut into tiles of T = EFES_CRC_BATCH_TILE bytes and the tiles, not the jobs,
+// are dealt to the workgroups.  The lengths live on the device, so the decomposition is done there,
+// in three stream-ordered launches over the caller's scratch:
+//   * batch_prep_kernel (one lane per job): a job's bulk is the np = (length - head) / 16 whole
+//     16-byte pieces behind its first 16-byte boundary; tiles(job) = ceil(np / 4096), 0 for a job
+//     that carries a SHA-1 state or no CRC state.  Writes the exclusive prefix sum of tiles() within
+//     each block of 1024 jobs (loc[]), the block's sum (bsum[]), and zeroes the job's two 4-byte
+//     accumulators.  Counts are 64-bit.
+//   * batch_tile_kernel (the hot path; one workgroup of 1024 lanes per CU): every workgroup scans
+//     bsum[] (<= 1024 entries) into LDS, which gives the tile total; workgroup w takes the
+//     consecutive tiles [w q, (w+1) q), q = ceil(total / G).  It finds its first tile's job by two
+//     counting passes (blocks, then the jobs of one block) and walks on from there: the next job with
+//     tiles is found by one coalesced read of 64 prefix entries per wave and a ballot, fetched while
+//     the current tile is hashed, as are the next tile's bytes.  Lane j of wave v reads the pieces
+//     256 v + 64 k + j (k = 0..3: four coalesced 1 KiB wave reads), takes each piece's raw CRC by
+//     slicing-by-4 from lane-private table copies in LDS (the layout of span_kernel) and folds
+//     acc = Z^stride(acc) ^ raw with two fixed byte-sliced operator tables (1024 bytes between a
+//     lane's pieces in a tile, T - 3072 to its first piece of the next tile).  A run of tiles of one
+//     job is folded this way without leaving the registers; at the end of a run each lane is
+//     advanced over the pieces that follow its last one (piece_op[]), the workgroup is XOR-reduced,
+//     advanced over the job's tiles behind the run (tile_op[], square-and-multiply beyond 256) and
+//     XORed into the job's accumulator with one atomic.  A job's LAST tile (whole or partial) is a
+//     run of its own and goes to the second accumulator, because what is still to be applied to it
+//     differs: acc_main waits for Z^(bytes of the last tile), acc_last for nothing.
+//   * batch_finish_kernel (one lane per job): head (< 16) and rest (< 16) bytes byte-wise
+//     (crc32.go:125), crc' = ~(Z^m(~crc_head) ^ Z^rest(Z^Lb(acc_main) ^ acc_last) ^ raw(rest)), and
+//     the state, sum and status stores exactly as the job kernels make them (efes_kernels.hip
+//     deep_rest) for a job without SHA-1; a job with a SHA-1 state gets EFES_ERR_ARG and nothing else.
+// No workgroup waits for another: stream order between the launches is the only dependency, and
+// every loop bound comes from memory the previous launch wrote.  Atomics go to the scratch only.
+// Plain HIP: no inline assembly, no LDS-DMA.
+//
+// Bound: HBM read, every byte once, plus per tile one 512-byte prefix read per wave, and per run one
+// gf2 product per lane and two or three on one lane.  Measured rates per shape, against the job
+// kernels and the span: DESIGN.md §4 "Batched CRC" (profiles/crc_batch/bench.json).
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   batch_prep_kernel     60 VGPRs, 22 SGPRs,    128 B LDS, no scratch, no spills, 8 waves/SIMD
+//   batch_tile_kernel    107 VGPRs, 97 SGPRs, 82 432 B LDS, no scratch, no spills, 4 waves/SIMD (one
+//                        1024-lane workgroup per CU; half of the CU's 160 KiB LDS)
+//   batch_finish_kernel   75 VGPRs, 29 SGPRs,      0 B LDS, no scratch, no spills, 6 waves/SIMD
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "efes_gf2.hpp"
+#include "efes_internal.hpp"
+
+namespace efes {
+
+namespace {
+
+constexpr uint64_t kTile = EFES_CRC_BATCH_TILE;
+constexpr int kPerLane = kBatchPieces / kBatchLanes;  // pieces of one tile per lane
+constexpr int kWaves = kBatchLanes / 64;
+constexpr uint32_t kPrefixBlock = 1024;  // jobs per block of the prefix sum
+constexpr uint32_t kMaxBlocks = EFES_CRC_BATCH_MAX_JOBS / kPrefixBlock;
+constexpr uint64_t kLaneStride = 16 * 64;  // bytes between a lane's pieces k and k + 1 (one 1 KiB wave read)
+constexpr uint64_t kTileStride = kTile - (kPerLane - 1) * kLaneStride;  // from piece kPerLane-1 to piece 0 of the next tile
+static_assert(kTile == 65536 && kPerLane == 4 && kLaneStride == 1024, "the piece layout below");
+static_assert(kMaxBlocks <= kBatchLanes, "one lane per block sum");
+static_assert(kTile * kBatchTileOps == (1ull << 24), "tile_op covers 2^24 bytes (batch_flush)");
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// Scratch: bsum[kMaxBlocks] | loc[njobs] | acc[njobs] (main, last).
+struct Scratch {
+  uint64_t* bsum;
+  uint64_t* loc;
+  uint2* acc;
+};
+__host__ __device__ inline Scratch scratch_of(void* p, uint32_t njobs) {
+  Scratch s;
+  s.bsum = static_cast<uint64_t*>(p);
+  s.loc = s.bsum + kMaxBlocks;
+  s.acc = reinterpret_cast<uint2*>(s.loc + njobs);
+  return s;
+}
+
+// A job's bytes: head (up to the first 16-byte boundary), np whole pieces at bulk, rest.
+struct Geo {
+  const uint8_t* bulk;
+  uint64_t np;
+  uint32_t head, rest;
+};
+__device__ __forceinline__ Geo job_geo(const void* data, uint64_t len) {
+  const uint8_t* d = static_cast<const uint8_t*>(data);
+  uint64_t head = (16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15;
+  if (len < head) head = len;
+  const uint64_t m = len - head;
+  Geo g;
+  g.bulk = d + head;
+  g.np = m >> 4;
+  g.head = (uint32_t)head;
+  g.rest = (uint32_t)(m & 15);
+  return g;
+}
+__device__ __forceinline__ uint64_t tiles_of(uint64_t np) { return (np + kBatchPieces - 1) / kBatchPieces; }
+
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+  return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v);
+}
+
+// Exclusive prefix sum of v over the workgroup's 1024 lanes (wsum: kWaves LDS words); *total = the sum.
+__device__ uint64_t block_scan_excl(uint64_t v, uint64_t* wsum, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint64_t inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint64_t o = __shfl_up(inc, off, 64);
+    if (lane >= (uint32_t)off) inc += o;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint64_t base = 0, tot = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < (uint32_t)kWaves; ++k) {
+    const uint64_t s = wsum[k];
+    if (k < wave) base += s;
+    tot += s;
+  }
+  __syncthreads();  // wsum may be written again
+  *total = tot;
+  return base + inc - v;
+}
+
+__global__ __launch_bounds__(kBatchLanes) void batch_prep_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                 void* scratch) {
+  __shared__ uint64_t wsum[kWaves];
+  const Scratch S = scratch_of(scratch, njobs);
+  const uint32_t j = blockIdx.x * kPrefixBlock + threadIdx.x;
+  uint64_t t = 0;
+  if (j < njobs) {
+    const efes_job* jb = jobs + j;
+    if (jb->sha1 == nullptr && jb->crc32 != nullptr) t = tiles_of(job_geo(jb->data, jb->length).np);
+    S.acc[j] = make_uint2(0u, 0u);
+  }
+  uint64_t total;
+  const uint64_t excl = block_scan_excl(t, wsum, &total);
+  if (j < njobs) S.loc[j] = excl;
+  if (threadIdx.x == 0) S.bsum[blockIdx.x] = total;
+}
+
+// LDS of the tile kernel: the slicing-by-4 tables in span_kernel's layout (entry e of table t, copy c
+// at byte 256 e + 64 t + 4 c; lane j reads copy j mod 16 and visits the tables in the order
+// (i + j / 16) mod 4, so no lookup instruction conflicts), the two stride operators, and the block
+// offsets of the prefix sum.  80.3 KiB: one workgroup per CU.
+constexpr int kCopies = 16;
+struct BatchLDS {
+  uint32_t lane_shift[4][256];  // Z^kLaneStride, byte-sliced
+  uint32_t tile_shift[4][256];  // Z^kTileStride
+  uint32_t slice[256][4][kCopies];
+  uint64_t boff[kMaxBlocks];
+  uint64_t wsum[kWaves];
+  uint32_t wave_sum[2][kWaves];
+};
+
+// Raw CRC (from a zero register) of one 16-byte piece: line_raw of efes_crc_span.hip, four words.
+__device__ __forceinline__ uint32_t piece_raw(const BatchLDS& L, uint32_t lb, const uint32_t (&sel)[4], v4u w) {
+  const char* base = reinterpret_cast<const char*>(&L.slice);
+  auto look = [&](uint32_t x, int i) {
+    return *reinterpret_cast<const uint32_t*>(base + __builtin_amdgcn_perm(x, lb, sel[i]));
+  };
+  uint32_t x = w.x;
+  uint32_t p = __builtin_amdgcn_bitop3_b32(look(x, 0), look(x, 1), look(x, 2), 0x96);
+  x = __builtin_amdgcn_bitop3_b32(p, look(x, 3), w.y, 0x96);
+  p = __builtin_amdgcn_bitop3_b32(look(x, 0), look(x, 1), look(x, 2), 0x96);
+  x = __builtin_amdgcn_bitop3_b32(p, look(x, 3), w.z, 0x96);
+  p = __builtin_amdgcn_bitop3_b32(look(x, 0), look(x, 1), look(x, 2), 0x96);
+  x = __builtin_amdgcn_bitop3_b32(p, look(x, 3), w.w, 0x96);
+  p = __builtin_amdgcn_bitop3_b32(look(x, 0), look(x, 1), look(x, 2), 0x96);
+  return p ^ look(x, 3);
+}
+
+// Z^stride(v) ^ raw from a byte-sliced operator table.
+__device__ __forceinline__ uint32_t shift_fold(const uint32_t (&s)[4][256], uint32_t v, uint32_t raw) {
+  const uint32_t p = __builtin_amdgcn_bitop3_b32(s[0][v & 0xffu], s[1][(v >> 8) & 0xffu], s[2][(v >> 16) & 0xffu], 0x96);
+  return __builtin_amdgcn_bitop3_b32(p, s[3][v >> 24], raw, 0x96);
+}
+
+// One tile of one job (wave-uniform): tile i of the job's nt, whose bulk holds np pieces.
+struct TileDesc {
+  uint32_t job;
+  uint64_t i, nt, np;
+  const uint8_t* bulk;
+};
+
+struct BatchArgs {
+  const efes_job* jobs;
+  void* scratch;
+  const Tables* tabs;
+  const BatchTables* batch;
+  uint32_t njobs, nblocks;
+};
+
+__device__ __forceinline__ void desc_of_job(const efes_job* __restrict__ jobs, uint32_t j, TileDesc& D) {
+  const Geo g = job_geo(reinterpret_cast<const void*>(uni64(reinterpret_cast<uint64_t>(jobs[j].data))), uni64(jobs[j].length));
+  D.job = j;
+  D.i = 0;
+  D.np = g.np;
+  D.nt = tiles_of(g.np);
+  D.bulk = g.bulk;
+}
+
+// The lane's pieces of tile D: piece 256 wave + 64 k + lane, zero where the bulk has ended.
+__device__ __forceinline__ void load_tile(const TileDesc& D, uint32_t first, v4u (&w)[kPerLane]) {
+  const uint64_t p0 = D.i * (uint64_t)kBatchPieces + first;
+  const __attribute__((address_space(1))) v4u* src =
+      (const __attribute__((address_space(1))) v4u*)D.bulk + p0;
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    v4u v = {0u, 0u, 0u, 0u};
+    if (p0 + 64u * k < D.np) v = src[64 * k];
+    w[k] = v;
+  }
+}
+
+__global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs a) {
+  __shared__ __attribute__((aligned(16))) BatchLDS L;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const Scratch S = scratch_of(a.scratch, a.njobs);
+  {  // tables into LDS: each slicing entry kCopies times, the two stride operators once
+    uint4* dst = reinterpret_cast<uint4*>(&L.slice);
+    for (uint32_t i = tid; i < sizeof(L.slice) / 16; i += kBatchLanes) {
+      const uint32_t word = 4 * i;  // entry word >> 6, table (word >> 4) & 3
+      const uint32_t v = a.tabs->slice8[(word >> 4) & 3u][word >> 6];
+      dst[i] = make_uint4(v, v, v, v);
+    }
+    const uint32_t e = (tid & 255u) << (8 * (tid >> 8));
+    L.lane_shift[tid >> 8][tid & 255u] = gf2_mulmod(a.batch->lane_stride_op, e);
+    L.tile_shift[tid >> 8][tid & 255u] = gf2_mulmod(a.batch->tile_stride_op, e);
+  }
+  uint64_t total;
+  {  // block offsets of the prefix sum, and the tile total
+    const uint64_t v = tid < a.nblocks ? S.bsum[tid] : 0;
+    L.boff[tid] = block_scan_excl(v, L.wsum, &total);
+  }
+  __syncthreads();
+  const uint64_t G = gridDim.x, q = (total + G - 1) / G;
+  const uint64_t t0 = (uint64_t)blockIdx.x * q;
+  if (t0 >= total) return;  // uniform over the workgroup (an empty batch: every workgroup)
+  const uint64_t t1 = t0 + q < total ? t0 + q : total;
+
+  // excl(idx): tiles before job idx; past the last job, more than any tile index
+  auto excl = [&](uint64_t idx) -> uint64_t {
+    return idx < a.njobs ? S.loc[idx] + L.boff[idx / kPrefixBlock] : ~0ull;
+  };
+  TileDesc D;
+  {  // the job of tile t0: the last block, then the last job of it, that starts at or before t0
+    const uint32_t b = (uint32_t)__syncthreads_count(tid < a.nblocks && L.boff[tid] <= t0) - 1u;
+    const uint64_t idx = (uint64_t)b * kPrefixBlock + tid;
+    const uint32_t j = b * kPrefixBlock + (uint32_t)__syncthreads_count(excl(idx) <= t0) - 1u;
+    desc_of_job(a.jobs, uni32(j), D);
+    D.i = t0 - uni64(excl(D.job));
+  }
+  // The job of tile t (> D's tile), which is not in D's job: the last job behind D.job that starts at
+  // or before t.  e = excl(base + lane), already loaded.
+  auto next_job = [&](uint32_t base, uint64_t e, uint64_t t) -> uint32_t {
+    for (;;) {
+      const uint32_t cnt = (uint32_t)__popcll(__ballot(e <= t));
+      if (cnt == 0u) return base < a.njobs ? base : a.njobs - 1u;  // not reached while loc[] is a prefix sum; stays in the array
+      if (cnt < 64u) return base + cnt - 1u;
+      base += 63u;  // 64 starts at or before t (jobs without tiles): go on from the last of them
+      e = excl((uint64_t)base + lane);
+    }
+  };
+
+  uint32_t lb = 0, sel[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t t = (uint32_t)(i + (int)(tid / 16)) & 3u;
+    lb |= (64u * t + 4u * (tid % kCopies)) << (8 * i);
+    sel[i] = 0x0C0C0000u | ((4u + 3u - t) << 8) | (uint32_t)i;
+  }
+  const uint32_t first = 256u * wave + lane;  // the lane's piece k = 0 of a tile
+
+  v4u cur[kPerLane];
+  load_tile(D, first, cur);
+  bool have_next = t0 + 1 < t1;
+  TileDesc N = D;
+  if (have_next) {
+    if (D.i + 1 < D.nt) {
+      N.i = D.i + 1;
+    } else {
+      const uint32_t base = D.job + 1u;
+      desc_of_job(a.jobs, next_job(base, excl((uint64_t)base + lane), t0 + 1), N);
+    }
+  }
+  uint32_t acc = 0, parity = 0;
+  for (uint64_t t = t0; t < t1; ++t) {
+    // ---- issue: the next tile's bytes, and what locates the tile after it
+    v4u nxt[kPerLane];
+    if (have_next) load_tile(N, first, nxt);
+    const bool have_next2 = t + 2 < t1;
+    const bool same2 = N.i + 1 < N.nt;
+    const uint32_t base2 = N.job + 1u;
+    uint64_t e2 = 0;
+    TileDesc spec = N;  // the job right behind N's, the usual successor
+    if (have_next2 && !same2) {
+      e2 = excl((uint64_t)base2 + lane);
+      desc_of_job(a.jobs, base2 < a.njobs ? base2 : a.njobs - 1u, spec);
+    }
+
+    // ---- hash tile D from cur
+    const uint64_t p0 = D.i * (uint64_t)kBatchPieces + first;
+    uint32_t kv = 0;  // the lane's pieces in this tile (a prefix of k = 0..3)
+#pragma unroll
+    for (int k = 0; k < kPerLane; ++k) {
+      if (p0 + 64u * k < D.np) {
+        const uint32_t raw = piece_raw(L, lb, sel, cur[k]);
+        acc = shift_fold(k == 0 ? L.tile_shift : L.lane_shift, acc, raw);
+        kv = k + 1;
+      }
+    }
+
+    // ---- the end of a run: D is its job's last tile, or the next tile does not continue the run
+    const bool last = D.i + 1 == D.nt;
+    const bool cont = !last && have_next && N.job == D.job && N.i + 1 != N.nt;
+    if (!cont) {
+      const uint64_t left = D.np - D.i * (uint64_t)kBatchPieces;
+      const uint32_t in_tile = left < (uint64_t)kBatchPieces ? (uint32_t)left : (uint32_t)kBatchPieces;
+      uint32_t c = 0;
+      if (kv) c = gf2_mulmod(a.batch->piece_op[in_tile - 1u - (first + 64u * (kv - 1u))], acc);
+      acc = 0;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) c ^= __shfl_xor(c, off, 64);
+      if (lane == 0) L.wave_sum[parity][wave] = c;
+      __syncthreads();
+      if (tid == 0) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int v = 0; v < kWaves; ++v) x ^= L.wave_sum[parity][v];
+        if (last) {
+          atomicXor(&S.acc[D.job].y, x);
+        } else {  // advance over the job's whole tiles behind this one, short of the last tile
+          const uint64_t after = D.nt - 2 - D.i;
+          x = gf2_mulmod(a.batch->tile_op[after % kBatchTileOps], x);
+          if (after / kBatchTileOps) x = gf2_mulmod(xpow8n((after / kBatchTileOps) << 24, a.batch->x2n), x);
+          atomicXor(&S.acc[D.job].x, x);
+        }
+      }
+      parity ^= 1u;  // the next run's sums go to the other half: lane 0 may still be reading this one
+    }
+
+    // ---- resolve the tile after next
+    TileDesc N2 = N;
+    if (have_next2) {
+      if (same2) {
+        N2.i = N.i + 1;
+      } else {
+        const uint32_t j2 = next_job(base2, e2, t + 2);
+        if (j2 == spec.job) N2 = spec;
+        else desc_of_job(a.jobs, j2, N2);
+      }
+    }
+    if (have_next) {
+#pragma unroll
+      for (int k = 0; k < kPerLane; ++k) cur[k] = nxt[k];
+    }
+    D = N;
+    N = N2;
+    have_next = have_next2;
+  }
+}
+
+__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
+
+__global__ __launch_bounds__(256) void batch_finish_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                           void* scratch, const Tables* __restrict__ tabs,
+                                                           const BatchTables* __restrict__ batch) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= njobs) return;
+  const efes_job jb = jobs[j];
+  if (jb.sha1 != nullptr) {  // not a CRC-only job: reported, nothing of it touched
+    if (jb.status) *jb.status = EFES_ERR_ARG;
+    return;
+  }
+  const bool do_crc = jb.crc32 != nullptr;
+  uint32_t crc = 0;
+  if (do_crc) {
+    const Scratch S = scratch_of(scratch, njobs);
+    const uint32_t* t0 = tabs->slice8[0];
+    const uint8_t* d = static_cast<const uint8_t*>(jb.data);
+    const Geo g = job_geo(jb.data, jb.length);
+    uint32_t r = (jb.flags & EFES_JOB_INIT) ? 0xFFFFFFFFu : ~jb.crc32->crc;  // crc32.go:123
+    for (uint32_t i = 0; i < g.head; ++i) r = t0[(r ^ d[i]) & 0xffu] ^ (r >> 8);  // crc32.go:125
+    const uint8_t* rest = g.bulk + 16 * g.np;
+    uint32_t tail = 0;  // raw CRC of the rest bytes from a zero register
+    for (uint32_t i = 0; i < g.rest; ++i) tail = t0[(tail ^ rest[i]) & 0xffu] ^ (tail >> 8);
+    uint32_t bulk = 0;
+    if (g.np) {
+      const uint2 acc = S.acc[j];
+      const uint64_t last_bytes = 16 * g.np - (tiles_of(g.np) - 1) * kTile;
+      bulk = gf2_mulmod(xpow8n(last_bytes, batch->x2n), acc.x) ^ acc.y;
+    }
+    const uint64_t m = jb.length - g.head;
+    crc = ~(gf2_mulmod(xpow8n(m, batch->x2n), r) ^ gf2_mulmod(xpow8n(g.rest, batch->x2n), bulk) ^ tail);
+    if (!(jb.flags & EFES_JOB_SUM_ONLY)) jb.crc32->crc = crc;
+  }
+  if ((jb.flags & EFES_JOB_FINALIZE) && jb.sum) {  // SHA-1 Sum (none: zeros) then CRC-32 Sum, big-endian
+    uint32_t* s = reinterpret_cast<uint32_t*>(jb.sum);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s[k] = 0u;
+    s[5] = bswap32(do_crc ? crc : 0u);
+  }
+  if (jb.status) *jb.status = EFES_OK;
+}
+
+}  // namespace
+
+void build_batch_tables(BatchTables* t) {
+  t->x2n[0] = 1u << 30;  // x^1
+  for (int k = 1; k < 32; ++k) t->x2n[k] = gf2_mulmod(t->x2n[k - 1], t->x2n[k - 1]);
+  const uint32_t piece = xpow8n(16), tile = xpow8n(kTile);
+  t->piece_op[0] = t->tile_op[0] = 1u << 31;  // x^0
+  for (int i = 1; i < kBatchPieces; ++i) t->piece_op[i] = gf2_mulmod(piece, t->piece_op[i - 1]);
+  for (int i = 1; i < kBatchTileOps; ++i) t->tile_op[i] = gf2_mulmod(tile, t->tile_op[i - 1]);
+  t->lane_stride_op = xpow8n(kLaneStride);
+  t->tile_stride_op = xpow8n(kTileStride);
+}
+
+size_t crc_batch_scratch_bytes(uint32_t njobs) {
+  if (njobs == 0 || njobs > EFES_CRC_BATCH_MAX_JOBS) return 0;
+  return sizeof(uint64_t) * kMaxBlocks + (sizeof(uint64_t) + sizeof(uint2)) * (size_t)njobs;
+}
+
+hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s) {
+  const uint32_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
+  clear_last_error();
+  hipLaunchKernelGGL(batch_prep_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  BatchArgs a{};
+  a.jobs = jobs;
+  a.scratch = scratch;
+  a.tabs = tabs;
+  a.batch = batch;
+  a.njobs = njobs;
+  a.nblocks = nblocks;
+  clear_last_error();
+  hipLaunchKernelGGL(batch_tile_kernel, dim3((uint32_t)(cus > 0 ? cus : 256)), dim3(kBatchLanes), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  clear_last_error();
+  hipLaunchKernelGGL(batch_finish_kernel, dim3((njobs + 255u) / 256u), dim3(256), 0, s, jobs, njobs, scratch, tabs, batch);
+  return hipGetLastError();
+}
+
+}  // namespace efes

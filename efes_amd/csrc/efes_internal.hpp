@@ -133,6 +133,25 @@ void build_span_tables(SpanTables* t);  // host
 hipError_t launch_crc_span(const void* data, uint64_t length, uint32_t* crc, const Tables* tabs, const SpanTables* span,
                            int cus, hipStream_t s);
 
+// Batched CRC (efes_crc_batch.hip): CRC-32 of many device buffers, each spread over the GPU in
+// tiles of EFES_CRC_BATCH_TILE bytes.  A tile is kBatchPieces 16-byte pieces; the per-context table
+// holds x2n[k] = x^(2^k) mod P (square-and-multiply on the device), piece_op[i] = x^(8*16*i) (a
+// lane's advance over the i pieces that follow its last one in a tile) and tile_op[a] =
+// x^(8*EFES_CRC_BATCH_TILE*a) (a workgroup's advance over the a tiles that follow its run).
+constexpr int kBatchLanes = 1024;
+constexpr int kBatchPieces = EFES_CRC_BATCH_TILE / 16;
+constexpr int kBatchTileOps = 256;
+struct BatchTables {
+  uint32_t x2n[32];
+  uint32_t piece_op[kBatchPieces];
+  uint32_t tile_op[kBatchTileOps];
+  uint32_t lane_stride_op, tile_stride_op;  // between a lane's consecutive pieces: in a tile, into the next tile
+};
+void build_batch_tables(BatchTables* t);  // host
+size_t crc_batch_scratch_bytes(uint32_t njobs);
+hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s);
+
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {
   switch (mode) {
@@ -181,6 +200,7 @@ struct efes_ctx {
   std::mutex plan_mu;             // one planned submit at a time uses the side streams/events
   efes::Tables* d_tabs = nullptr;
   efes::SpanTables* d_span = nullptr;  // operators of the span CRC (efes_crc32_span)
+  efes::BatchTables* d_batch = nullptr;  // operators of the batched CRC (efes_crc32_batch)
   std::mutex mu;                  // guards the lazy creation of `digests` and `copy`
   efes_queue* digests = nullptr;  // shared queue of the streaming digests (efes_stream.cpp)
   hipStream_t copy = nullptr;     // efes_hash_host's H2D stream (own_queue_stream), created on first use

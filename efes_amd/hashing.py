@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -41,6 +41,12 @@ def plan_batch(lengths, ctx: "Context | None" = None) -> tuple[np.ndarray, Plan]
                                 lengths.size, order.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(plan)),
           "efes_plan_batch")
     return order, plan
+
+
+def crc32_batch_scratch(n: int) -> int:
+    """efes_crc32_batch_scratch: device bytes efes_crc32_batch needs for n jobs (0 for n == 0 or more
+    than EFES_CRC_BATCH_MAX_JOBS)."""
+    return int(lib().efes_crc32_batch_scratch(n))
 
 
 class Context:
@@ -78,6 +84,13 @@ class Context:
         """efes_crc32_span: crc32.go Write (76-86) of one long device buffer into the device CRC state
         at crc_state_ptr, segment-parallel over the whole GPU (asynchronous on `stream`)."""
         check(lib().efes_crc32_span(self.handle, data_ptr, nbytes, crc_state_ptr, stream), "efes_crc32_span")
+
+    def crc32_batch(self, jobs_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
+                    stream: int | None = None) -> None:
+        """efes_crc32_batch: the CRC-only jobs (sha1 == NULL) of a device job array, their bytes dealt
+        to the whole GPU in tiles; scratch: crc32_batch_scratch(njobs) device bytes, 16-byte aligned,
+        one buffer per call that may overlap another (asynchronous on `stream`)."""
+        check(lib().efes_crc32_batch(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_batch")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

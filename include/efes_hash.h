@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define EFES_ABI_VERSION 7
+#define EFES_ABI_VERSION 8
 
 /* ---- error codes ---------------------------------------------------------------- */
 #define EFES_OK 0
@@ -380,6 +380,43 @@ uint32_t efes_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
  * context stream); calls that share a state must be ordered on one stream. */
 int efes_crc32_span(efes_ctx* ctx, const void* data_device, uint64_t length, efes_crc32_state* crc_device,
                     void* stream);
+
+/* CRC-32 of MANY device buffers in one call (ABI 8): njobs efes_job records in device memory, exactly
+ * as for efes_hash_submit, each with sha1 == NULL.  For every such job the call writes what
+ * efes_hash_submit writes for it -- crc32->crc, the 24-byte sum under EFES_JOB_FINALIZE (20 zero
+ * bytes, then the CRC big-endian), status; EFES_JOB_INIT and EFES_JOB_SUM_ONLY as above; crc32 == NULL
+ * hashes nothing; any data alignment, any length -- but the bytes of ALL jobs are cut into tiles of
+ * EFES_CRC_BATCH_TILE bytes that are dealt evenly to the whole GPU, so a few long buffers, or long and
+ * short ones mixed, take the time of their total size, not of the longest job on one wavefront.  A
+ * job with sha1 != NULL gets status EFES_ERR_ARG and nothing else of it is written; its neighbours
+ * are unaffected.  Jobs of one call must not share a state.  The lengths are read on the device:
+ * the host reads back nothing, allocates nothing and waits for nothing.  Asynchronous on `stream`
+ * (NULL = the context stream).
+ * scratch_device: device memory of the context's GPU, 16-byte aligned, at least
+ * efes_crc32_batch_scratch(njobs) bytes (0 for njobs == 0 or > EFES_CRC_BATCH_MAX_JOBS), used in stream
+ * order from the call until its work is done: calls that may overlap (different streams) need a
+ * scratch buffer each; calls on one stream may share one.
+ * Returns EFES_ERR_ARG for a NULL ctx, NULL jobs with njobs > 0, njobs > EFES_CRC_BATCH_MAX_JOBS (split
+ * the batch), and scratch that is NULL, too small or misaligned; njobs == 0 returns EFES_OK and
+ * launches nothing.
+ * Which CRC path when (measured on 4 GiB per shape, profiles/crc_batch/bench.json; DESIGN.md §4
+ * "Batched CRC" has the table):
+ *   - ONE long buffer: efes_crc32_span.  Its LDS-DMA reads stay ahead: the batch call reads the same
+ *     4 GiB object at about 0.85 of the span's rate;
+ *   - two or more buffers of 1 MiB and up, of equal or of mixed sizes (objects re-checked after a copy
+ *     or drain, the pieces of shard.py): efes_crc32_batch.  It holds about 0.7 of the 8 TB/s spec from
+ *     16 x 256 MiB down to 1024 x 4 MiB, where CRC-only jobs of efes_hash_submit give each buffer one
+ *     wavefront and run 150x (16 buffers) to 2.5x (1024) slower, and one span call per buffer takes
+ *     1.1x (16 buffers) to 1.8x (64) as long;
+ *   - very many small buffers (65 536 x 64 KiB: one tile per job): CRC-only jobs of efes_hash_submit,
+ *     whose WIDE shape hashes one buffer per lane at about twice the batch call's rate there (the
+ *     batch call ends a run, with a workgroup barrier, at every tile);
+ *   - CRC jobs mixed with SHA-1 jobs in one array: efes_hash_submit (the batch call refuses them). */
+#define EFES_CRC_BATCH_TILE 65536u
+#define EFES_CRC_BATCH_MAX_JOBS (1u << 20)
+size_t efes_crc32_batch_scratch(uint32_t njobs);
+int efes_crc32_batch(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
+                     size_t scratch_bytes, void* stream);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
