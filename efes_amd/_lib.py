@@ -29,6 +29,7 @@ EFES_ERR_DEVICE_FAULT = -7
 EFES_JOB_FINALIZE = 0x1
 EFES_JOB_INIT = 0x2
 EFES_JOB_SUM_ONLY = 0x4
+EFES_JOB_CHAIN = 0x8  # efes_crc32_chain: the next Write into the state of the job before it
 EFES_HASH_SHA1, EFES_HASH_CRC32 = 0x1, 0x2
 EFES_HOST_ZERO_COPY = (1 << 64) - 1
 EFES_CRC_BATCH_TILE = 65536  # bytes of one job that one workgroup CRCs at a time (efes_crc32_batch)
@@ -172,6 +173,8 @@ SIGNATURES = {
     "efes_crc32_span": (_I, [_VP, _VP, _U64, _VP, _VP]),
     "efes_crc32_batch_scratch": (_S, [_U32]),
     "efes_crc32_batch": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
+    "efes_crc32_chain_scratch": (_S, [_U32]),
+    "efes_crc32_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),
     "efes_crc32_state_marshal_text": (None, [_P(Crc32State), _VP]),

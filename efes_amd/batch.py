@@ -9,9 +9,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
+from ._lib import (EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, default_context
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -209,6 +209,90 @@ class DeviceBatch:
 
     def states_host(self) -> np.ndarray:
         return self.states.cpu().numpy().view(SHA1_STATE_DTYPE)[: self.n]
+
+
+class DeviceObjects:
+    """CRC-32 of objects that lie in many device extents, in one efes_crc32_chain call.
+
+    objects[i] is a list of (offset, length) extents of the buffer at data_ptr, in the object's byte
+    order: one job per extent and one state per object, the first extent's job the chain's head
+    (with EFES_JOB_INIT when `fresh`, else starting from crcs[i]), the others with EFES_JOB_CHAIN.
+    EFES_JOB_FINALIZE goes on the last extent of each object, or on every extent when `running` (the
+    CRC after each extent, what `.info` holds after each PATCH).  An object without extents takes no
+    job and keeps its in-state.  Ordered with torch's current stream as DeviceBatch is.
+    """
+
+    _ordered = DeviceBatch._ordered
+
+    def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
+                 running: bool = False, ctx: Context | None = None, device: str = "cuda:0"):
+        import torch
+
+        self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
+        self.torch = torch
+        self.device = device
+        objects = [list(o) for o in objects]
+        self.nobjects = len(objects)
+        counts = np.array([len(o) for o in objects], dtype=np.int64)
+        n = self.n = int(counts.sum())
+        self.first = np.concatenate(([0], np.cumsum(counts)))[:-1] if self.nobjects else np.zeros(0, np.int64)
+        self.last = self.first + counts - 1  # job of each object's last extent (first - 1: no extents)
+        ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
+        owner = np.repeat(np.arange(self.nobjects, dtype=np.uint64), counts)
+        self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
+        assert self.init_crcs.size == self.nobjects
+        self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
+        self.crcs = self._init_crcs_dev.clone() if self.nobjects else torch.zeros(4, dtype=torch.uint8, device=device)
+        self.sums = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=device)
+        self.status = torch.full((max(n, 1),), -99, dtype=torch.int32, device=device)
+        idx = np.arange(n, dtype=np.uint64)
+        jobs = np.zeros(n, dtype=JOB_DTYPE)
+        jobs["data"] = np.uint64(data_ptr) + ext[:, 0]
+        jobs["length"] = ext[:, 1]
+        jobs["crc32"] = np.uint64(self.crcs.data_ptr()) + owner * np.uint64(4)
+        jobs["sum"] = np.uint64(self.sums.data_ptr()) + idx * np.uint64(24)
+        jobs["status"] = np.uint64(self.status.data_ptr()) + idx * np.uint64(4)
+        jobs["flags"] = EFES_JOB_CHAIN
+        heads = self.first[counts > 0]
+        jobs["flags"][heads] = EFES_JOB_INIT if fresh else 0
+        if running:
+            jobs["flags"] |= EFES_JOB_FINALIZE
+        else:
+            jobs["flags"][self.last[counts > 0]] |= EFES_JOB_FINALIZE
+        self.running = bool(running)
+        self.jobs_host = jobs
+        self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
+        # allocated once and kept: one object set's launches run in stream order
+        self._scratch = torch.empty(max(crc32_chain_scratch(n), 16), dtype=torch.uint8, device=device)
+        torch.cuda.synchronize(device)
+
+    def reset(self) -> None:
+        """Restore the initial states (async, on torch's current stream)."""
+        if self.nobjects:
+            self.crcs.copy_(self._init_crcs_dev)
+
+    def submit(self) -> None:
+        self._ordered(lambda stream: self.ctx.crc32_chain(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
+                                                          self._scratch.numel(), stream))
+
+    def run(self) -> None:
+        self.submit()
+        self.torch.cuda.synchronize(self.device)
+
+    # ---- results (host copies)
+    def status_host(self) -> np.ndarray:
+        """Per extent."""
+        return self.status.cpu().numpy()[: self.n]
+
+    def crc_sum(self) -> np.ndarray:
+        """Per object: the state after its last extent."""
+        return self.crcs.cpu().numpy().view(np.uint32)[: self.nobjects]
+
+    def running_crcs(self) -> np.ndarray:
+        """Per extent: the object's CRC at that extent's end (a set built with running=True)."""
+        if not self.running:
+            raise ValueError("running_crcs: build the set with running=True")
+        return self.sums.cpu().numpy()[: self.n * 24].reshape(self.n, 24)[:, 20:].copy().view(">u4").reshape(-1).astype(np.uint32)
 
 
 class PinnedHostBuffer:

@@ -1,5 +1,5 @@
 // efes_crc_batch.hip -- CRC-32/IEEE of MANY device buffers in one call, each spread over the whole GPU
-// (efes_crc32_batch, ABI 8).
+// (efes_crc32_batch, ABI 8), and of objects that lie in many extents (efes_crc32_chain, further down).
 //
 // CRC-only jobs of efes_hash_submit run in the SHA-1-shaped kernels, one wavefront per job at best,
 // although CRC-32 is GF(2)-linear and needs no chain (efes_crc_span.hip has the identities).  Here
@@ -43,6 +43,32 @@
 //   batch_tile_kernel    107 VGPRs, 97 SGPRs, 82 432 B LDS, no scratch, no spills, 4 waves/SIMD (one
 //                        1024-lane workgroup per CU; half of the CU's 160 KiB LDS)
 //   batch_finish_kernel   75 VGPRs, 29 SGPRs,      0 B LDS, no scratch, no spills, 6 waves/SIMD
+//
+// Chained jobs (efes_crc32_chain): a job with EFES_JOB_CHAIN is the next Write into the state of the
+// job before it, so one object may lie in many extents.  The prep and tile kernels run unchanged (an
+// extent is dealt to the workgroups as the same extent would be as a job of its own); the finish pass
+// is replaced by a scan.  A job of n bytes takes the raw register r to m (x) r ^ b with m = x^(8n) and
+// b = the raw CRC of its bytes from a zero register; a head folds its in-state into b and has m = 0,
+// so it drops whatever stands before it and chains need no segment flags.  Validity rides along as
+// bad' = (a & bad) | c (a: the job is chained, c: it is invalid by itself).  Maps compose as
+// (m2,b2,a2,c2) o (m1,b1,a1,c1) = (m2 (x) m1, m2 (x) b1 ^ b2, a2 & a1, (a2 & c1) | c2), so the register
+// and the bad bit after every job are an inclusive scan, in three stream-ordered launches over
+// 16-byte elements behind the batch scratch:
+//   * chain_map_kernel (one lane per job, 1024 jobs per workgroup): builds the job's map from its
+//     head and rest bytes and the two accumulators (as batch_finish_kernel combines them), reads the
+//     in-state of a head, scans the workgroup (wave shuffles, then the 16 wave totals through LDS) and
+//     stores elem[job] and the block's total.  States are read here and written only by
+//     chain_finish_kernel, so the two never race.
+//   * chain_carry_kernel (one workgroup, one lane per block, whole waves): scans the <= 1024 block totals
+//     in place.  Skipped for one block.
+//   * chain_finish_kernel (one lane per job): applies the carry of the blocks before; an invalid job
+//     gets EFES_ERR_ARG and nothing else; a valid one its sum under FINALIZE and its status, and the
+//     tail of a chain (the last job, or one whose successor is unflagged or invalid by itself) stores
+//     the state.
+// No workgroup waits for another here either.
+//   chain_map_kernel      68 VGPRs, 43 SGPRs,    256 B LDS, no scratch, no spills, 7 waves/SIMD
+//   chain_carry_kernel    68 VGPRs, 39 SGPRs,    256 B LDS, no scratch, no spills, 7 waves/SIMD
+//   chain_finish_kernel   50 VGPRs, 20 SGPRs,      0 B LDS, no scratch, no spills, 8 waves/SIMD
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -410,6 +436,181 @@ __global__ __launch_bounds__(256) void batch_finish_kernel(const efes_job* __res
   if (jb.status) *jb.status = EFES_OK;
 }
 
+// ---- chained jobs (efes_crc32_chain): prep and tile kernels as above, then map / carry / finish ----
+
+// Both products a * b0 and a * b1 mod P in one pass: the product commutes, so the bits are taken from
+// b0 and b1 and the one shifted operand, a, serves both (7 operations a step instead of gf2_mulmod's 10).
+__device__ __forceinline__ void gf2_mulmod2(uint32_t a, uint32_t b0, uint32_t b1, uint32_t& p0, uint32_t& p1) {
+  uint32_t q0 = 0, q1 = 0;
+  for (int i = 0; i < 32; ++i) {
+    q0 ^= a & (0u - ((b0 >> (31 - i)) & 1u));
+    q1 ^= a & (0u - ((b1 >> (31 - i)) & 1u));
+    a = (a >> 1) ^ (kPolyReflected & (0u - (a & 1u)));
+  }
+  p0 = q0;
+  p1 = q1;
+}
+
+// What a job does to the pair (raw register r, bad bit): r -> m (x) r ^ b, bad -> (a & bad) | c.
+// f holds a in bit 0 and c in bit 1.  A head has m = 0 and a = 0: whatever came before it is dropped.
+struct Aff {
+  uint32_t m, b, f;
+};
+constexpr uint32_t kAffPass = 1u, kAffBad = 2u;
+__device__ __forceinline__ Aff aff_identity() { return Aff{1u << 31, 0u, kAffPass}; }
+// hi after lo.
+__device__ __forceinline__ Aff aff_compose(const Aff& hi, const Aff& lo) {
+  Aff r;
+  uint32_t pb;
+  gf2_mulmod2(hi.m, lo.m, lo.b, r.m, pb);
+  r.b = pb ^ hi.b;
+  r.f = (hi.f & lo.f & kAffPass) | ((hi.f & kAffPass) ? (lo.f & kAffBad) : 0u) | (hi.f & kAffBad);
+  return r;
+}
+__device__ __forceinline__ uint4 aff_pack(const Aff& e) { return make_uint4(e.m, e.b, e.f, 0u); }
+__device__ __forceinline__ Aff aff_unpack(const uint4 v) { return Aff{v.x, v.y, v.z}; }
+
+// Inclusive scan of e over `width` (<= 64) lanes of a wave, in job order.
+__device__ __forceinline__ Aff wave_scan_incl(Aff e, uint32_t lane, int width) {
+  for (int off = 1; off < width; off <<= 1) {
+    Aff lo;
+    lo.m = __shfl_up(e.m, off, 64);
+    lo.b = __shfl_up(e.b, off, 64);
+    lo.f = __shfl_up(e.f, off, 64);
+    if (lane >= (uint32_t)off) e = aff_compose(e, lo);
+  }
+  return e;
+}
+
+// Inclusive scan over the workgroup's lanes (a multiple of 64, up to 1024): wave shuffles, then the
+// wave totals through LDS (wave 0 scans them).  Every lane of the workgroup calls it.
+__device__ Aff block_scan_aff(Aff e, uint4* wtot) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  e = wave_scan_incl(e, lane, 64);
+  if (nwaves == 1u) return e;  // uniform over the workgroup
+  if (lane == 63u) wtot[wave] = aff_pack(e);
+  __syncthreads();
+  if (wave == 0u) {
+    const Aff t = wave_scan_incl(lane < nwaves ? aff_unpack(wtot[lane]) : aff_identity(), lane, kWaves);
+    if (lane < nwaves) wtot[lane] = aff_pack(t);
+  }
+  __syncthreads();
+  if (wave) e = aff_compose(e, aff_unpack(wtot[wave - 1u]));
+  return e;
+}
+
+// Chain scratch: the batch scratch | elem[njobs] | btot[blocks of kPrefixBlock jobs], 16 bytes each.
+struct ChainScratch {
+  uint4* elem;
+  uint4* btot;
+};
+__host__ __device__ inline size_t batch_scratch_size(uint32_t njobs) {
+  return sizeof(uint64_t) * kMaxBlocks + (sizeof(uint64_t) + sizeof(uint2)) * (size_t)njobs;
+}
+__host__ __device__ inline ChainScratch chain_scratch_of(void* p, uint32_t njobs) {
+  static_assert((sizeof(uint64_t) * kMaxBlocks) % 16 == 0 && sizeof(uint64_t) + sizeof(uint2) == 16, "elem[] stays 16-byte aligned");
+  ChainScratch c;
+  c.elem = reinterpret_cast<uint4*>(static_cast<char*>(p) + batch_scratch_size(njobs));
+  c.btot = c.elem + njobs;
+  return c;
+}
+
+// A job with EFES_JOB_CHAIN behind the job (prev_crc32, prev_flags), j > 0: not a Write into that job's state.
+__device__ __forceinline__ bool follower_bad(const efes_job& jb, const efes_crc32_state* prev_crc32, uint32_t prev_flags) {
+  return jb.sha1 != nullptr || jb.crc32 == nullptr || jb.crc32 != prev_crc32 ||
+         (jb.flags & (EFES_JOB_INIT | EFES_JOB_SUM_ONLY)) != 0u || (prev_flags & EFES_JOB_SUM_ONLY) != 0u;
+}
+
+__global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                void* scratch, const Tables* __restrict__ tabs,
+                                                                const BatchTables* __restrict__ batch) {
+  __shared__ uint4 wtot[kWaves];
+  const uint32_t j = blockIdx.x * kPrefixBlock + threadIdx.x;
+  const ChainScratch C = chain_scratch_of(scratch, njobs);
+  Aff e = aff_identity();  // the lanes past the array
+  if (j < njobs) {
+    const efes_job jb = jobs[j];
+    const bool chained = (jb.flags & EFES_JOB_CHAIN) != 0u;
+    bool bad = jb.sha1 != nullptr;
+    if (chained) bad = j == 0u || follower_bad(jb, jobs[j - 1u].crc32, jobs[j - 1u].flags);
+    e = Aff{0u, 0u, (chained ? kAffPass : 0u) | (bad ? kAffBad : 0u)};
+    if (!bad && jb.crc32 != nullptr) {
+      const Scratch S = scratch_of(scratch, njobs);
+      const uint32_t* t0 = tabs->slice8[0];
+      const uint8_t* d = static_cast<const uint8_t*>(jb.data);
+      const Geo g = job_geo(jb.data, jb.length);
+      // The register after the head bytes: from the in-state for a head (crc32.go:123), whose map then
+      // forgets what came before (m = 0), from zero for a follower.
+      uint32_t r = 0;
+      if (!chained) r = (jb.flags & EFES_JOB_INIT) ? 0xFFFFFFFFu : ~jb.crc32->crc;
+      for (uint32_t i = 0; i < g.head; ++i) r = t0[(r ^ d[i]) & 0xffu] ^ (r >> 8);  // crc32.go:125
+      const uint32_t behind_head = xpow8n(jb.length - g.head, batch->x2n);
+      if (r) r = gf2_mulmod(behind_head, r);
+      uint32_t t = 0;  // the bulk's raw CRC from the two accumulators, as batch_finish_kernel combines them
+      if (g.np) {
+        const uint2 acc = S.acc[j];
+        const uint64_t nt = tiles_of(g.np);
+        t = acc.y;
+        if (nt > 1) t ^= gf2_mulmod(xpow8n(16 * g.np - (nt - 1) * kTile, batch->x2n), acc.x);
+      }
+      // one table step is x^8: going on byte-wise from t gives Z^rest(bulk) ^ raw(rest)
+      const uint8_t* rest = g.bulk + 16 * g.np;
+      for (uint32_t i = 0; i < g.rest; ++i) t = t0[(t ^ rest[i]) & 0xffu] ^ (t >> 8);
+      e.b = r ^ t;
+      if (chained) {  // m = x^(8 length): the head's zero bytes applied to x^(8 (length - head))
+        e.m = behind_head;
+        for (uint32_t i = 0; i < g.head; ++i) e.m = t0[e.m & 0xffu] ^ (e.m >> 8);
+      }
+    }
+  }
+  e = block_scan_aff(e, wtot);
+  if (j < njobs) C.elem[j] = aff_pack(e);
+  if (threadIdx.x == kPrefixBlock - 1u) C.btot[blockIdx.x] = aff_pack(e);
+}
+
+// btot[k] becomes the map of the blocks 0..k together.  One workgroup of at least nblocks lanes.
+__global__ __launch_bounds__(kBatchLanes) void chain_carry_kernel(uint32_t njobs, uint32_t nblocks, void* scratch) {
+  __shared__ uint4 wtot[kWaves];
+  const ChainScratch C = chain_scratch_of(scratch, njobs);
+  const uint32_t k = threadIdx.x;
+  const Aff e = block_scan_aff(k < nblocks ? aff_unpack(C.btot[k]) : aff_identity(), wtot);
+  if (k < nblocks) C.btot[k] = aff_pack(e);
+}
+
+__global__ __launch_bounds__(256) void chain_finish_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                           void* scratch) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= njobs) return;
+  const ChainScratch C = chain_scratch_of(scratch, njobs);
+  const efes_job jb = jobs[j];
+  Aff e = aff_unpack(C.elem[j]);
+  const uint32_t blk = j / kPrefixBlock;
+  if (blk) {  // nothing comes before job 0: register 0, not bad
+    const Aff carry = aff_unpack(C.btot[blk - 1u]);
+    e.b ^= gf2_mulmod(e.m, carry.b);
+    e.f |= (e.f & kAffPass) ? (carry.f & kAffBad) : 0u;
+  }
+  if (e.f & kAffBad) {  // not a Write into its chain's state: reported, nothing of it touched
+    if (jb.status) *jb.status = EFES_ERR_ARG;
+    return;
+  }
+  const bool do_crc = jb.crc32 != nullptr;
+  const uint32_t crc = ~e.b;  // the CRC after this job's Write
+  bool tail = j + 1u == njobs;
+  if (!tail) {
+    const efes_job nx = jobs[j + 1u];
+    tail = !(nx.flags & EFES_JOB_CHAIN) || follower_bad(nx, jb.crc32, jb.flags);
+  }
+  if (do_crc && tail && !(jb.flags & EFES_JOB_SUM_ONLY)) jb.crc32->crc = crc;
+  if ((jb.flags & EFES_JOB_FINALIZE) && jb.sum) {  // as batch_finish_kernel
+    uint32_t* s = reinterpret_cast<uint32_t*>(jb.sum);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) s[k] = 0u;
+    s[5] = bswap32(do_crc ? crc : 0u);
+  }
+  if (jb.status) *jb.status = EFES_OK;
+}
+
 }  // namespace
 
 void build_batch_tables(BatchTables* t) {
@@ -425,11 +626,12 @@ void build_batch_tables(BatchTables* t) {
 
 size_t crc_batch_scratch_bytes(uint32_t njobs) {
   if (njobs == 0 || njobs > EFES_CRC_BATCH_MAX_JOBS) return 0;
-  return sizeof(uint64_t) * kMaxBlocks + (sizeof(uint64_t) + sizeof(uint2)) * (size_t)njobs;
+  return batch_scratch_size(njobs);
 }
 
-hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
-                            const BatchTables* batch, int cus, hipStream_t s) {
+// The two launches every path starts with: tiles per job, then the tiles.
+static hipError_t launch_prep_and_tiles(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                                        const BatchTables* batch, int cus, hipStream_t s) {
   const uint32_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
   clear_last_error();
   hipLaunchKernelGGL(batch_prep_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch);
@@ -444,10 +646,41 @@ hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch,
   a.nblocks = nblocks;
   clear_last_error();
   hipLaunchKernelGGL(batch_tile_kernel, dim3((uint32_t)(cus > 0 ? cus : 256)), dim3(kBatchLanes), 0, s, a);
-  e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s) {
+  hipError_t e = launch_prep_and_tiles(jobs, njobs, scratch, tabs, batch, cus, s);
   if (e != hipSuccess) return e;
   clear_last_error();
   hipLaunchKernelGGL(batch_finish_kernel, dim3((njobs + 255u) / 256u), dim3(256), 0, s, jobs, njobs, scratch, tabs, batch);
+  return hipGetLastError();
+}
+
+size_t crc_chain_scratch_bytes(uint32_t njobs) {
+  if (njobs == 0 || njobs > EFES_CRC_BATCH_MAX_JOBS) return 0;
+  const size_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
+  return batch_scratch_size(njobs) + sizeof(uint4) * ((size_t)njobs + nblocks);
+}
+
+hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s) {
+  const uint32_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
+  hipError_t e = launch_prep_and_tiles(jobs, njobs, scratch, tabs, batch, cus, s);
+  if (e != hipSuccess) return e;
+  clear_last_error();
+  hipLaunchKernelGGL(chain_map_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch, tabs, batch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (nblocks > 1) {  // one block of jobs has no carry to take
+    clear_last_error();
+    hipLaunchKernelGGL(chain_carry_kernel, dim3(1), dim3((nblocks + 63u) / 64u * 64u), 0, s, njobs, nblocks, scratch);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  clear_last_error();
+  hipLaunchKernelGGL(chain_finish_kernel, dim3((njobs + 255u) / 256u), dim3(256), 0, s, jobs, njobs, scratch);
   return hipGetLastError();
 }
 

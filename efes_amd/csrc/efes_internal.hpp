@@ -151,6 +151,11 @@ void build_batch_tables(BatchTables* t);  // host
 size_t crc_batch_scratch_bytes(uint32_t njobs);
 hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
                             const BatchTables* batch, int cus, hipStream_t s);
+// Chained CRC jobs (efes_crc32_chain): the same prep and tile launches, then a scan of the jobs'
+// affine maps over the scratch (the batch scratch plus 16 bytes per job and per 1024 jobs).
+size_t crc_chain_scratch_bytes(uint32_t njobs);
+hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

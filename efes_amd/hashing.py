@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -47,6 +47,12 @@ def crc32_batch_scratch(n: int) -> int:
     """efes_crc32_batch_scratch: device bytes efes_crc32_batch needs for n jobs (0 for n == 0 or more
     than EFES_CRC_BATCH_MAX_JOBS)."""
     return int(lib().efes_crc32_batch_scratch(n))
+
+
+def crc32_chain_scratch(n: int) -> int:
+    """efes_crc32_chain_scratch: device bytes efes_crc32_chain needs for n jobs (0 for n == 0 or more
+    than EFES_CRC_BATCH_MAX_JOBS; never less than crc32_batch_scratch(n))."""
+    return int(lib().efes_crc32_chain_scratch(n))
 
 
 class Context:
@@ -91,6 +97,13 @@ class Context:
         to the whole GPU in tiles; scratch: crc32_batch_scratch(njobs) device bytes, 16-byte aligned,
         one buffer per call that may overlap another (asynchronous on `stream`)."""
         check(lib().efes_crc32_batch(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_batch")
+
+    def crc32_chain(self, jobs_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
+                    stream: int | None = None) -> None:
+        """efes_crc32_chain: efes_crc32_batch that honours EFES_JOB_CHAIN -- a flagged job is the next
+        Write into the state of the job before it, so one object may lie in many extents; scratch:
+        crc32_chain_scratch(njobs) device bytes, otherwise as for crc32_batch."""
+        check(lib().efes_crc32_chain(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_chain")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

@@ -94,6 +94,8 @@ void* efes_ctx_stream(efes_ctx* ctx);
 #define EFES_JOB_SUM_ONLY 0x4u /* with EFES_JOB_FINALIZE and length 0: Sum of the in-state on a copy
                                   (sha1.go:82-87 `d0 := *d`): the states are read, never written, so
                                   a pending full tail (nx == 64) stays pending as in Go */
+#define EFES_JOB_CHAIN 0x8u    /* efes_crc32_chain only: this job is the next Write into the CRC state of
+                                  the job before it (below); every other call ignores the bit */
 
 /* One `Write(p)` (+ optional Sum) of len(p) = length bytes at device address `data`.
  * sha1 / crc32: device states updated in place; either may be NULL to skip that hash
@@ -416,6 +418,51 @@ int efes_crc32_span(efes_ctx* ctx, const void* data_device, uint64_t length, efe
 #define EFES_CRC_BATCH_MAX_JOBS (1u << 20)
 size_t efes_crc32_batch_scratch(uint32_t njobs);
 int efes_crc32_batch(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
+                     size_t scratch_bytes, void* stream);
+
+/* Chained CRC jobs: ONE object in MANY device extents (PATCH-sized chunks, staging chunks, the pieces
+ * of shard.py, extents of a buffer pool).  efes_crc32_chain is efes_crc32_batch -- the same device job
+ * array, lengths read on the device, no host read-back, allocation or wait, asynchronous on `stream`,
+ * the same argument errors, njobs <= EFES_CRC_BATCH_MAX_JOBS, njobs == 0 returns EFES_OK and launches
+ * nothing, the same scratch rules with efes_crc32_chain_scratch(njobs) bytes (>= the batch call's) --
+ * that also honours EFES_JOB_CHAIN:
+ *   - a chain is a head job (flag clear) and the consecutive jobs behind it that carry the flag; its
+ *     members are Write(p0); Write(p1); ... (crc32.go:76-86) into the one state they all name.  An
+ *     unflagged job is a chain of one: for an array without the flag the call writes byte for byte what
+ *     efes_crc32_batch writes.  Chains of one call must not share a state with each other;
+ *   - the head may carry EFES_JOB_INIT, or starts from the state's value;
+ *   - every member with EFES_JOB_FINALIZE gets its own 24-byte sum: 20 zero bytes, then the CRC after
+ *     THAT member's Write, big-endian -- the running CRC of the object at that extent's end, what
+ *     `.info` holds after each PATCH (fileinfo.go:10-58).  A zero-length FINALIZE member gives the sum
+ *     EFES_JOB_SUM_ONLY would;
+ *   - crc32->crc is written once, by the chain's last valid member, with the CRC after its Write;
+ *   - every member gets a status;
+ *   - a flagged job is invalid when it is job 0, has sha1 != NULL or crc32 == NULL, names another state
+ *     than the job before it, also carries EFES_JOB_INIT or EFES_JOB_SUM_ONLY, follows an
+ *     EFES_JOB_SUM_ONLY job, or follows an invalid member of its chain; a head with sha1 != NULL is
+ *     invalid as in the batch call.  An invalid member gets status EFES_ERR_ARG and nothing else of it
+ *     is written (its data bytes may be read).  The valid members before it have taken effect, as the
+ *     Writes before a panicking Write have in Go; the next chain is unaffected.
+ * The extents are dealt to the GPU exactly as the same extents would be as separate jobs of
+ * efes_crc32_batch; the Writes are then composed on the device as affine maps of the CRC register by a
+ * parallel prefix scan (DESIGN.md §4 "Chained CRC").
+ * Other calls: efes_crc32_batch and the efes_hash_submit family ignore EFES_JOB_CHAIN as they ignore
+ * every unknown bit, so there the flagged jobs are independent jobs and "jobs in one submit must not
+ * share a state" still holds; efes_hash_host rejects unknown flags.  EFES_ABI_VERSION stays 8: the
+ * addition changes nothing that existed, and a binding detects it by the symbol.
+ * Which CRC path when, continued (measured on 4 GiB per shape, profiles/crc_chain/bench.json; DESIGN.md
+ * §4 "Chained CRC" has the table):
+ *   - objects that lie in several extents each (64 objects x 64 extents x 1 MiB and 1024 objects x 64
+ *     extents x 64 KiB measured): efes_crc32_chain.  On the device it takes the time of efes_crc32_batch
+ *     over the same extents as separate jobs, within 5 % either way, and the object CRCs (and the CRC
+ *     after every extent, where asked) are ready on the device.  efes_crc32_batch into piece states,
+ *     then a copy of the piece CRCs to the host and efes_crc32_combine per piece there, has the object
+ *     CRCs on the host about 15x (4096 extents) to 100x (65 536 extents) later, the fold measured through
+ *     the Python binding; one efes_crc32_span per extent on one stream takes about 70x to 400x as long;
+ *   - an array without EFES_JOB_CHAIN: either call; efes_crc32_batch is some 30 us (4 % of 4 GiB at
+ *     1024 x 4 MiB) shorter, the cost of scanning instead of one finish launch. */
+size_t efes_crc32_chain_scratch(uint32_t njobs);
+int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
                      size_t scratch_bytes, void* stream);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
