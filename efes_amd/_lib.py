@@ -29,11 +29,12 @@ EFES_ERR_DEVICE_FAULT = -7
 EFES_JOB_FINALIZE = 0x1
 EFES_JOB_INIT = 0x2
 EFES_JOB_SUM_ONLY = 0x4
-EFES_JOB_CHAIN = 0x8  # efes_crc32_chain: the next Write into the state of the job before it
+EFES_JOB_CHAIN = 0x8  # efes_crc32_chain / efes_hash_chain: the next Write into the state of the job before it
 EFES_HASH_SHA1, EFES_HASH_CRC32 = 0x1, 0x2
 EFES_HOST_ZERO_COPY = (1 << 64) - 1
 EFES_CRC_BATCH_TILE = 65536  # bytes of one job that one workgroup CRCs at a time (efes_crc32_batch)
 EFES_CRC_BATCH_MAX_JOBS = 1 << 20
+EFES_HASH_CHAIN_MAX_JOBS = 1 << 20
 MODE_AUTO, MODE_DEEP, MODE_WIDE = 0, 1, 2
 MODE_GROUP = {4: 3, 8: 4, 16: 5, 32: 6}  # grouped DEEP: lanes per job -> EFES_MODE_GROUPn
 MODE_FED4 = 7  # grouped DEEP fed by producer waves on other SIMDs (EFES_MODE_FED4: 2 chains + 2 producers)
@@ -175,6 +176,8 @@ SIGNATURES = {
     "efes_crc32_batch": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_crc32_chain_scratch": (_S, [_U32]),
     "efes_crc32_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
+    "efes_hash_chain_scratch": (_S, [_U32]),
+    "efes_hash_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),
     "efes_crc32_state_marshal_text": (None, [_P(Crc32State), _VP]),

@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context, hash_chain_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -212,7 +212,8 @@ class DeviceBatch:
 
 
 class DeviceObjects:
-    """CRC-32 of objects that lie in many device extents, in one efes_crc32_chain call.
+    """CRC-32 (and, with sha1=True, SHA-1) of objects that lie in many device extents, in one call:
+    efes_crc32_chain for the default CRC-only set, efes_hash_chain for a set built with sha1=True.
 
     objects[i] is a list of (offset, length) extents of the buffer at data_ptr, in the object's byte
     order: one job per extent and one state per object, the first extent's job the chain's head
@@ -220,13 +221,25 @@ class DeviceObjects:
     EFES_JOB_FINALIZE goes on the last extent of each object, or on every extent when `running` (the
     CRC after each extent, what `.info` holds after each PATCH).  An object without extents takes no
     job and keeps its in-state.  Ordered with torch's current stream as DeviceBatch is.
+
+    sha1=True keeps one 104-byte SHA-1 state per object as well (NewSha1(), or states[i]) and hashes
+    through efes_hash_chain, one wavefront per object: fused with crc32=True, SHA-1 alone with
+    crc32=False.  Then sha1_hex() is the Sum at each object's last extent, running_sha1() the Sum at
+    every extent's end (running=True) and states_host() the states, stale tail bytes included.
     """
 
     _ordered = DeviceBatch._ordered
 
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
-                 running: bool = False, ctx: Context | None = None, device: str = "cuda:0"):
+                 running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
+                 crc32: bool = True, states: np.ndarray | None = None):
         import torch
+
+        if not (sha1 or crc32):
+            raise ValueError("DeviceObjects: sha1 or crc32 (or both)")
+        if states is not None and not sha1:
+            raise ValueError("DeviceObjects: states= needs sha1=True")
+        self.has_sha1, self.has_crc32 = bool(sha1), bool(crc32)
 
         self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
         self.torch = torch
@@ -249,7 +262,14 @@ class DeviceObjects:
         jobs = np.zeros(n, dtype=JOB_DTYPE)
         jobs["data"] = np.uint64(data_ptr) + ext[:, 0]
         jobs["length"] = ext[:, 1]
-        jobs["crc32"] = np.uint64(self.crcs.data_ptr()) + owner * np.uint64(4)
+        if crc32:
+            jobs["crc32"] = np.uint64(self.crcs.data_ptr()) + owner * np.uint64(4)
+        if sha1:
+            self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
+            assert self.init_states.size == self.nobjects
+            self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
+            self.states = self._init_states_dev.clone() if self.nobjects else torch.zeros(104, dtype=torch.uint8, device=device)
+            jobs["sha1"] = np.uint64(self.states.data_ptr()) + owner * np.uint64(104)
         jobs["sum"] = np.uint64(self.sums.data_ptr()) + idx * np.uint64(24)
         jobs["status"] = np.uint64(self.status.data_ptr()) + idx * np.uint64(4)
         jobs["flags"] = EFES_JOB_CHAIN
@@ -263,17 +283,21 @@ class DeviceObjects:
         self.jobs_host = jobs
         self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
         # allocated once and kept: one object set's launches run in stream order
-        self._scratch = torch.empty(max(crc32_chain_scratch(n), 16), dtype=torch.uint8, device=device)
+        scratch_bytes = hash_chain_scratch(n) if sha1 else crc32_chain_scratch(n)
+        self._scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=device)
         torch.cuda.synchronize(device)
 
     def reset(self) -> None:
         """Restore the initial states (async, on torch's current stream)."""
         if self.nobjects:
             self.crcs.copy_(self._init_crcs_dev)
+            if self.has_sha1:
+                self.states.copy_(self._init_states_dev)
 
     def submit(self) -> None:
-        self._ordered(lambda stream: self.ctx.crc32_chain(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
-                                                          self._scratch.numel(), stream))
+        call = self.ctx.hash_chain if self.has_sha1 else self.ctx.crc32_chain
+        self._ordered(lambda stream: call(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
+                                          self._scratch.numel(), stream))
 
     def run(self) -> None:
         self.submit()
@@ -293,6 +317,28 @@ class DeviceObjects:
         if not self.running:
             raise ValueError("running_crcs: build the set with running=True")
         return self.sums.cpu().numpy()[: self.n * 24].reshape(self.n, 24)[:, 20:].copy().view(">u4").reshape(-1).astype(np.uint32)
+
+    def _need_sha1(self, what: str) -> None:
+        if not self.has_sha1:
+            raise ValueError(f"{what}: build the set with sha1=True")
+
+    def sha1_hex(self) -> list:
+        """Per object: the SHA-1 Sum at its last extent's end (None for an object without extents)."""
+        self._need_sha1("sha1_hex")
+        s = self.sums.cpu().numpy()[: self.n * 24].reshape(self.n, 24)
+        return [bytes(s[int(j), :20]).hex() if j >= f else None for f, j in zip(self.first, self.last)]
+
+    def running_sha1(self) -> list:
+        """Per extent: the object's SHA-1 Sum at that extent's end (a set built with running=True)."""
+        self._need_sha1("running_sha1")
+        if not self.running:
+            raise ValueError("running_sha1: build the set with running=True")
+        return [bytes(r[:20]).hex() for r in self.sums.cpu().numpy()[: self.n * 24].reshape(self.n, 24)]
+
+    def states_host(self) -> np.ndarray:
+        """Per object: the SHA-1 state after its last extent (h, x with its stale bytes, nx, len)."""
+        self._need_sha1("states_host")
+        return self.states.cpu().numpy().view(SHA1_STATE_DTYPE)[: self.nobjects]
 
 
 class PinnedHostBuffer:

@@ -377,6 +377,18 @@ int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* 
   return hip_err(efes::launch_crc_chain(jobs, njobs, scratch, ctx->d_tabs, ctx->d_batch, ctx->cus, pick(ctx, stream)));
 }
 
+size_t efes_hash_chain_scratch(uint32_t njobs) { return efes::hash_chain_scratch_bytes(njobs); }
+
+int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+  if (!ctx || (!jobs && njobs) || njobs > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::hash_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_hash_chain(jobs, njobs, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
+}
+
 int efes_crc32_tables(uint32_t* out, size_t nwords) {
   const size_t need = sizeof(Tables) / 4, with_pos = need + sizeof(efes::PosTables) / 4;
   if (!out || nwords < need) return EFES_ERR_ARG;

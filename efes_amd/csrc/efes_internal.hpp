@@ -156,6 +156,12 @@ hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch,
 size_t crc_chain_scratch_bytes(uint32_t njobs);
 hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
                             const BatchTables* batch, int cus, hipStream_t s);
+// Chained SHA-1 + CRC jobs (efes_hash_chain, efes_kernels.hip): two prep launches list the chains'
+// heads in the scratch (16 bytes, 4 per block of 1024 jobs at the maximum count, 8 per job), then a
+// persistent launch in which each wavefront draws whole chains by a ticket.
+size_t hash_chain_scratch_bytes(uint32_t njobs);
+hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs, int cus,
+                             hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

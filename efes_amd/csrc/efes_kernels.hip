@@ -1638,4 +1638,210 @@ hipError_t launch_fill(void* dst, size_t bytes, uint64_t seed, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ================================================================== chained jobs (efes_hash_chain)
+// An object that lies in k extents is k Writes into one digest pair; through efes_hash_submit that is
+// k stream-ordered launches, each as long as its longest job.  Here a job with EFES_JOB_CHAIN is the
+// next Write into the states of the job before it, and one wavefront walks a whole chain: SHA-1 is
+// serial within an object, not across objects.  Three stream-ordered launches over the caller's scratch:
+//   * hash_chain_mark_kernel (one lane per job, 1024 jobs per workgroup): a job is a head when it is
+//     job 0 or carries no EFES_JOB_CHAIN.  Writes the exclusive count of heads before each job within
+//     its block (loc[]), the block's count (bsum[]), and zeroes the ticket.
+//   * hash_chain_list_kernel (same grid): every workgroup sums the bsum[] of the blocks before it and
+//     stores its heads' job indices at heads[base + loc], in job order; the last one stores the count.
+//   * hash_chain_kernel (persistent; four waves per workgroup, one per SIMD, one workgroup per CU;
+//     Tables in LDS once per workgroup, 64 B of x and 192 B of padding area per wave): a wave draws a chain with one atomic add
+//     on the ticket (lane 0, broadcast), leaves when the ticket reaches the count, and runs the members
+//     [heads[t], heads[t + 1]) in order through the one-wave job path, deep_head + deep_rest<true>,
+//     exactly as a grouped wave runs a job that is left alone -- not deep_kernel's producer/consumer
+//     pipeline, whose LDS hand-shake is per job.  An unflagged job is a chain of one and gets what
+//     EFES_MODE_DEEP writes.  Validity is tracked on the way: a flagged job that is job 0, names other
+//     states than the member before it, names none, carries INIT or SUM_ONLY, or follows a SUM_ONLY
+//     job or an invalid member gets EFES_ERR_ARG and nothing else.
+// The state stays in memory between members: deep_rest stores it with some lanes, the next deep_head
+// loads it with all of them.  After each member the wave drains its stores, passes an agent-scope
+// fence and waits again (the wait behind the fence is kept on purpose: the compiler may drop the
+// fence's own).  The state pointers carry no const/__restrict__, so their loads stay vector loads,
+// which the fence covers (scalar-cache loads it would not refresh).
+// No wave waits for another: stream order is the only dependency between the launches and every loop
+// bound comes from memory an earlier launch wrote, or from the ticket.  No LDS-DMA; the only inline
+// assembly is that wait.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   hash_chain_mark_kernel    36 VGPRs,  16 SGPRs,     64 B LDS, no scratch, no spills, 8 waves/SIMD
+//   hash_chain_list_kernel    18 VGPRs,  20 SGPRs,     64 B LDS, no scratch, no spills, 8 waves/SIMD
+//   hash_chain_kernel        143 VGPRs, 106 SGPRs, 87 040 B LDS, no scratch, no VGPR spills, 2 SGPRs kept in
+//                            VGPR lanes (as group_kernel<4>), 1 wave/SIMD (one workgroup per CU, by LDS)
+// deep_kernel, group_kernel<*>, fed_kernel<*> and wide_kernel compile to the same registers, LDS, scratch
+// and occupancy with and without this section.
+constexpr uint32_t kChainBlock = 1024;  // jobs per block of the head count
+constexpr uint32_t kChainMaxBlocks = EFES_HASH_CHAIN_MAX_JOBS / kChainBlock;
+static_assert(kChainMaxBlocks <= kChainBlock, "one lane per block count in hash_chain_list_kernel");
+
+// Scratch: ctl (16 bytes) | bsum[kChainMaxBlocks] | loc[njobs] | heads[njobs], 32-bit words.
+struct ChainCtl {
+  uint32_t count;   // chains of this call (hash_chain_list_kernel)
+  uint32_t ticket;  // next chain to take (zeroed by hash_chain_mark_kernel on every call)
+  uint32_t pad[2];
+};
+struct HashChainScratch {
+  ChainCtl* ctl;
+  uint32_t* bsum;
+  uint32_t* loc;
+  uint32_t* heads;
+};
+__host__ __device__ inline HashChainScratch hash_chain_scratch_of(void* p, uint32_t njobs) {
+  HashChainScratch s;
+  s.ctl = static_cast<ChainCtl*>(p);
+  s.bsum = reinterpret_cast<uint32_t*>(s.ctl + 1);
+  s.loc = s.bsum + kChainMaxBlocks;
+  s.heads = s.loc + njobs;
+  return s;
+}
+
+// Sum of v over the workgroup's 1024 lanes, and this lane's exclusive prefix (wsum: 16 LDS words).
+__device__ uint32_t chain_block_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t o = __shfl_up(inc, off, 64);
+    if (lane >= (uint32_t)off) inc += o;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < kChainBlock / 64; ++k) {
+    const uint32_t s = wsum[k];
+    if (k < wave) base += s;
+    tot += s;
+  }
+  __syncthreads();  // wsum may be written again
+  *total = tot;
+  return base + inc - v;
+}
+
+__device__ __forceinline__ bool chain_is_head(const efes_job* jobs, uint32_t j) {
+  return j == 0u || (jobs[j].flags & EFES_JOB_CHAIN) == 0u;
+}
+
+__global__ __launch_bounds__(kChainBlock) void hash_chain_mark_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                      void* scratch) {
+  __shared__ uint32_t wsum[kChainBlock / 64];
+  const HashChainScratch S = hash_chain_scratch_of(scratch, njobs);
+  const uint32_t j = blockIdx.x * kChainBlock + threadIdx.x;
+  const uint32_t head = j < njobs && chain_is_head(jobs, j) ? 1u : 0u;
+  uint32_t total;
+  const uint32_t excl = chain_block_scan(head, wsum, &total);
+  if (j < njobs) S.loc[j] = excl;
+  if (threadIdx.x == 0) {
+    S.bsum[blockIdx.x] = total;
+    if (blockIdx.x == 0) S.ctl->ticket = 0u;
+  }
+}
+
+__global__ __launch_bounds__(kChainBlock) void hash_chain_list_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                      void* scratch) {
+  __shared__ uint32_t wsum[kChainBlock / 64];
+  const HashChainScratch S = hash_chain_scratch_of(scratch, njobs);
+  uint32_t base;  // heads in the blocks before this one
+  (void)chain_block_scan(threadIdx.x < blockIdx.x ? S.bsum[threadIdx.x] : 0u, wsum, &base);
+  const uint32_t j = blockIdx.x * kChainBlock + threadIdx.x;
+  if (j < njobs && chain_is_head(jobs, j)) S.heads[base + S.loc[j]] = j;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) S.ctl->count = base + S.bsum[blockIdx.x];
+}
+
+struct ChainLDS {
+  Tables tab;                    // 36 KiB
+  uint8_t xs[kDeepWaves][64];    // each wave's tail buffer x
+  uint8_t fin[kDeepWaves][192];  // padding assembly for checkSum
+  // Never touched: lifts the workgroup over half of the CU's LDS, so a CU holds ONE of these workgroups
+  // and a SIMD one chain.  By registers three would fit, and the tickets then put up to three chains on
+  // one SIMD while others stay empty: 1024 chains of 4 MiB took 137 ms instead of 48, and 4096 chains
+  // gained nothing (the SIMD's issue rate is the bound either way).  DESIGN.md §4 "Chained SHA-1 + CRC".
+  uint8_t own_cu[48 * 1024];
+};
+static_assert(sizeof(ChainLDS) > kCuLds / 2 && sizeof(ChainLDS) <= 96 * 1024, "one chain workgroup per CU");
+
+__global__ __launch_bounds__(64 * kDeepWaves) void hash_chain_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                     const Tables* __restrict__ tabs, void* scratch) {
+  __shared__ __attribute__((aligned(16))) ChainLDS L;
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(tabs);
+    uint4* dst = reinterpret_cast<uint4*>(&L.tab);
+    for (int i = threadIdx.x; i < (int)(sizeof(Tables) / 16); i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int wave = (int)uniform32(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const HashChainScratch S = hash_chain_scratch_of(scratch, njobs);
+  const uint32_t count = uniform32(S.ctl->count);
+  for (;;) {
+    uint32_t t = 0;
+    if (lane == 0) t = atomicAdd(&S.ctl->ticket, 1u);
+    t = uniform32(t);
+    if (t >= count) break;
+    const uint32_t first = uniform32(S.heads[t]);
+    uint32_t end = njobs;
+    if (t + 1u < count) end = uniform32(S.heads[t + 1u]);
+    end = end < njobs ? end : njobs;
+    bool bad = false, wrote = false;
+    const efes_sha1_state* prev_st = nullptr;  // the member before: the states it names, its flags
+    const efes_crc32_state* prev_cs = nullptr;
+    uint32_t prev_flags = 0;
+    for (uint32_t j = first; j < end; ++j) {
+      const DeepJob J = load_job(jobs, j, lane);
+      if (J.flags & EFES_JOB_CHAIN)  // j == first: job 0, a follower of nothing
+        bad = bad || j == first || J.st != prev_st || J.cs != prev_cs || (J.st == nullptr && J.cs == nullptr) ||
+              (J.flags & (EFES_JOB_INIT | EFES_JOB_SUM_ONLY)) != 0u || (prev_flags & EFES_JOB_SUM_ONLY) != 0u;
+      if (bad) {  // not a Write into its chain's state: reported, nothing of it touched
+        if (lane == 0 && J.status) *J.status = EFES_ERR_ARG;
+        continue;
+      }
+      if (wrote) {  // the member before stored the state this one loads
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      const DeepMsg M = deep_head(L.tab, lane, J, L.xs[wave]);
+      if (M.live) deep_rest<true>(L.tab, lane, J, L.xs[wave], L.fin[wave], M);
+      wrote = true;
+      prev_st = J.st;
+      prev_cs = J.cs;
+      prev_flags = J.flags;
+    }
+  }
+}
+
+size_t hash_chain_scratch_bytes(uint32_t njobs) {
+  if (njobs == 0 || njobs > EFES_HASH_CHAIN_MAX_JOBS) return 0;
+  const size_t b = sizeof(ChainCtl) + sizeof(uint32_t) * ((size_t)kChainMaxBlocks + 2 * (size_t)njobs);
+  return (b + 15) & ~(size_t)15;
+}
+
+hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs, int cus,
+                             hipStream_t s) {
+  if (njobs == 0) return hipSuccess;
+  const uint32_t nblocks = (njobs + kChainBlock - 1) / kChainBlock;
+  clear_last_error();
+  hipLaunchKernelGGL(hash_chain_mark_kernel, dim3(nblocks), dim3(kChainBlock), 0, s, jobs, njobs, scratch);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  clear_last_error();
+  hipLaunchKernelGGL(hash_chain_list_kernel, dim3(nblocks), dim3(kChainBlock), 0, s, jobs, njobs, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // Persistent grid: the chain count lives on the device, so the grid is sized by the job count and
+  // by what is resident at once (a workgroup that starts late finds the tickets gone and leaves).
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hash_chain_kernel, 64 * kDeepWaves, 0) != hipSuccess ||
+      per_cu < 1)
+    per_cu = 1;
+  const uint64_t resident = (uint64_t)(cus > 0 ? cus : 256) * (uint64_t)per_cu;
+  const uint64_t want = ((uint64_t)njobs + kDeepWaves - 1) / kDeepWaves;
+  clear_last_error();
+  hipLaunchKernelGGL(hash_chain_kernel, dim3((uint32_t)std::min(want, resident)), dim3(64 * kDeepWaves), 0, s, jobs,
+                     njobs, tabs, scratch);
+  return hipGetLastError();
+}
+
 }  // namespace efes

@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "hash_chain_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -53,6 +53,12 @@ def crc32_chain_scratch(n: int) -> int:
     """efes_crc32_chain_scratch: device bytes efes_crc32_chain needs for n jobs (0 for n == 0 or more
     than EFES_CRC_BATCH_MAX_JOBS; never less than crc32_batch_scratch(n))."""
     return int(lib().efes_crc32_chain_scratch(n))
+
+
+def hash_chain_scratch(n: int) -> int:
+    """efes_hash_chain_scratch: device bytes efes_hash_chain needs for n jobs (0 for n == 0 or more than
+    EFES_HASH_CHAIN_MAX_JOBS)."""
+    return int(lib().efes_hash_chain_scratch(n))
 
 
 class Context:
@@ -104,6 +110,14 @@ class Context:
         Write into the state of the job before it, so one object may lie in many extents; scratch:
         crc32_chain_scratch(njobs) device bytes, otherwise as for crc32_batch."""
         check(lib().efes_crc32_chain(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_chain")
+
+    def hash_chain(self, jobs_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
+                   stream: int | None = None) -> None:
+        """efes_hash_chain: fused, SHA-1-only or CRC-only jobs as for submit(), with EFES_JOB_CHAIN honoured
+        -- a flagged job is the next Write into the states of the job before it, and one wavefront walks
+        each chain, so an object in many extents takes one call; scratch: hash_chain_scratch(njobs) device
+        bytes, 16-byte aligned, one buffer per call that may overlap another (asynchronous on `stream`)."""
+        check(lib().efes_hash_chain(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_hash_chain")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

@@ -94,8 +94,8 @@ void* efes_ctx_stream(efes_ctx* ctx);
 #define EFES_JOB_SUM_ONLY 0x4u /* with EFES_JOB_FINALIZE and length 0: Sum of the in-state on a copy
                                   (sha1.go:82-87 `d0 := *d`): the states are read, never written, so
                                   a pending full tail (nx == 64) stays pending as in Go */
-#define EFES_JOB_CHAIN 0x8u    /* efes_crc32_chain only: this job is the next Write into the CRC state of
-                                  the job before it (below); every other call ignores the bit */
+#define EFES_JOB_CHAIN 0x8u    /* efes_crc32_chain and efes_hash_chain only: this job is the next Write into
+                                  the state(s) of the job before it (below); every other call ignores the bit */
 
 /* One `Write(p)` (+ optional Sum) of len(p) = length bytes at device address `data`.
  * sha1 / crc32: device states updated in place; either may be NULL to skip that hash
@@ -464,6 +464,66 @@ int efes_crc32_batch(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs,
 size_t efes_crc32_chain_scratch(uint32_t njobs);
 int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
                      size_t scratch_bytes, void* stream);
+
+/* Chained SHA-1 + CRC-32 jobs: efes_hash_submit for objects that lie in MANY device extents.  The same
+ * device job array as efes_hash_submit, fused, SHA-1-only or CRC-only jobs, lengths and flags read on
+ * the device, no host read-back, allocation or wait, asynchronous on `stream` (NULL = the context
+ * stream); njobs <= EFES_HASH_CHAIN_MAX_JOBS.  The call honours EFES_JOB_CHAIN, and its yardstick is Go's
+ * Write; Write; ... into one digest pair: what njobs successive efes_hash_submit_mode(EFES_MODE_DEEP)
+ * calls of one job each, on one stream, would leave behind.
+ *   - a chain is a head job (flag clear) and the consecutive jobs behind it that carry the flag; its
+ *     members are successive Writes into the one sha1 and/or crc32 state they all name (either pointer
+ *     may be NULL for the whole chain).  Chains of one call must not share a state with each other;
+ *   - the head takes every flag efes_hash_submit knows (EFES_JOB_INIT, EFES_JOB_FINALIZE,
+ *     EFES_JOB_SUM_ONLY).  An unflagged job is a chain of one: for an array without the flag the call
+ *     writes byte for byte what efes_hash_submit_mode(EFES_MODE_DEEP) writes -- the states with their
+ *     stale bytes x[nx:64], the sums, the statuses;
+ *   - every member with EFES_JOB_FINALIZE gets its own 24-byte sum from the state after THAT member's
+ *     Write: SHA-1 Sum on a copy (sha1.go:82-87), then the CRC big-endian -- the running digest of the
+ *     object at that extent's end, what `.info` holds after each PATCH (fileinfo.go:10-58).  Members of
+ *     length zero are allowed;
+ *   - after the call the states hold what they hold after the valid members' Writes in order (h, x
+ *     with its stale bytes, nx, len, crc); whether intermediate values are stored on the way is
+ *     unspecified;
+ *   - every member gets a status.  EFES_ERR_STATE arises where the job kernels raise it: with nx > 64
+ *     at a Write (sha1.go:62) that member writes nothing else, and the members behind it find the same
+ *     state and get the same status, as successive Writes would; d.nx != 0 at Sum (sha1.go:107-109)
+ *     gives EFES_ERR_STATE with the state written;
+ *   - a flagged job is invalid when it is job 0, names a sha1 or a crc32 pointer other than the job
+ *     before it, has both pointers NULL, also carries EFES_JOB_INIT or EFES_JOB_SUM_ONLY, follows an
+ *     EFES_JOB_SUM_ONLY job, or follows an invalid member of its chain.  An invalid member gets status
+ *     EFES_ERR_ARG and nothing else of it is written.  The valid members before it have taken effect;
+ *     the next chain is unaffected.
+ * scratch_device: device memory of the context's GPU, 16-byte aligned, at least
+ * efes_hash_chain_scratch(njobs) bytes (0 for njobs == 0 or > EFES_HASH_CHAIN_MAX_JOBS), used in stream
+ * order from the call until its work is done: calls that may overlap (different streams) need a
+ * scratch buffer each; calls on one stream may share one.
+ * Returns EFES_ERR_ARG for a NULL ctx, NULL jobs with njobs > 0, njobs > EFES_HASH_CHAIN_MAX_JOBS (split
+ * the array between chains), and scratch that is NULL, too small or misaligned; njobs == 0 returns
+ * EFES_OK and launches nothing.
+ * The chains are found on the device (two small launches list the heads); then every wavefront of a
+ * persistent launch draws whole chains and runs their members in order on the one-wave path of the
+ * DEEP shape, so a call lasts as long as its longest chains, not as the sum over extent steps of the
+ * longest extent in each (DESIGN.md §4 "Chained SHA-1 + CRC").  EFES_ABI_VERSION stays 8: the addition
+ * changes nothing that existed, and a binding detects it by the symbol.
+ * Which path when (measured, profiles/hash_chain/bench.json; DESIGN.md §4 "Chained SHA-1 + CRC" has the
+ * table; "steps" = one efes_hash_submit per extent step on one stream, one job per object that still has
+ * an extent, AUTO or forced DEEP):
+ *   - objects of UNEQUAL extent counts or sizes, no more of them than SIMDs (1024 objects of 1-64 extents
+ *     of 4 KiB-1 MiB, longest first): efes_hash_chain.  It takes about 0.6 of the steps' device time: the
+ *     longest object's own chain instead of the sum over steps of the longest extent in each;
+ *   - objects of EQUAL extents, no more of them than SIMDs (1024 objects x 16 x 256 KiB, x 128 x 32 KiB):
+ *     either.  On the device the chain call takes 3 to 4 % and 2 % longer than the steps -- its waves
+ *     run without DEEP's producer wave -- and is one call instead of 16 or 128;
+ *   - more objects than SIMDs (4096 objects x 16 x 64 KiB): the steps through efes_hash_submit (AUTO).
+ *     The chain call runs one chain per SIMD at a time and takes about 3.8 times as long as AUTO's FED4
+ *     launches there (2 % longer than the steps forced to DEEP);
+ *   - an array without EFES_JOB_CHAIN (1024 x 4 MiB): efes_hash_submit; the chain call takes 3 to 4 %
+ *     longer than EFES_MODE_DEEP for the same bytes. */
+#define EFES_HASH_CHAIN_MAX_JOBS (1u << 20)
+size_t efes_hash_chain_scratch(uint32_t njobs);
+int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
+                    size_t scratch_bytes, void* stream);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 

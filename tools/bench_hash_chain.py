@@ -1,0 +1,188 @@
+"""Chained SHA-1 + CRC-32 jobs against what a caller had before, in one GPU run: writes
+profiles/hash_chain/bench.json and bench.log beside it.
+
+    python tools/bench_hash_chain.py [--out PATH] [--seconds 1.0] [--shapes 0,1,2,3,4]
+
+Synthetic bytes in a 4 GiB pool (well past the 256 MiB Infinity Cache), fused jobs, every repetition from
+NewSha1() / NewCRC32IEEE().  The paths alternate in this process, each warmed once and then repeated until
+its device-event-timed work reaches --seconds:
+  (a) chain -- one efes_hash_chain call over all extents, one state pair per object;
+  (b) steps -- what a caller does without it: one efes_hash_submit (AUTO) per extent step on one stream,
+      with one job per object that still has an extent;
+  (c) steps-deep -- the same launches forced to EFES_MODE_DEEP.
+Shapes: 1024 objects x 16 extents x 256 KiB (a 4 MiB PATCH in staging chunks); 1024 x 128 x 32 KiB
+(io.Copy-sized Writes); a seeded ragged set, 1024 objects of 1-64 extents of 4 KiB-1 MiB, longest object
+first; 4096 x 16 x 64 KiB (more chains than SIMDs); 1024 x 4 MiB with no job flagged, where (b) and (c) are
+one efes_hash_submit(AUTO) / efes_hash_submit_mode(DEEP) of the same array.
+Before any rate is printed every path's status must be EFES_OK, the objects' 24-byte sums of all paths
+must be equal, and two objects per shape must match hashlib and zlib.
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import os
+import sys
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+POOL = 4 << 30
+
+
+def equal_shape(nobj: int, next_: int, size: int):
+    """Per object: [(offset, length)] -- the pool cut into consecutive extents, object after object."""
+    assert nobj * next_ * size == POOL
+    return [[((i * next_ + k) * size, size) for k in range(next_)] for i in range(nobj)]
+
+
+def ragged_shape(seed: int = 0x4A66ED):
+    """1024 objects of 1-64 extents of 4 KiB-1 MiB at seeded 4 KiB-aligned pool offsets, longest object first."""
+    rng = np.random.default_rng(seed)
+    objects = []
+    for _ in range(1024):
+        k = int(rng.integers(1, 65))
+        lens = rng.integers(4 << 10, (1 << 20) + 1, size=k)
+        offs = rng.integers(0, (POOL - (1 << 20)) >> 12, size=k) << 12
+        objects.append([(int(o), int(n)) for o, n in zip(offs, lens)])
+    objects.sort(key=lambda o: -sum(n for _, n in o))
+    return objects
+
+
+SHAPES = [("1024 objects x 16 extents x 256 KiB", lambda: equal_shape(1024, 16, 256 << 10)),
+          ("1024 objects x 128 extents x 32 KiB", lambda: equal_shape(1024, 128, 32 << 10)),
+          ("ragged: 1024 objects x 1-64 extents x 4 KiB-1 MiB, longest first", ragged_shape),
+          ("4096 objects x 16 extents x 64 KiB", lambda: equal_shape(4096, 16, 64 << 10)),
+          ("1024 x 4 MiB, unflagged", lambda: equal_shape(1024, 1, 4 << 20))]
+
+
+def stats(total: int, dev: list[float]) -> dict:
+    """Repetition 0 is the warm-up."""
+    d = sorted(dev[1:])
+    med = d[len(d) // 2]
+    return {"reps": len(d), "device_seconds_median": round(med, 6), "device_seconds_min": round(d[0], 6),
+            "device_seconds_max": round(d[-1], 6), "spread_min_max_over_median": [round(d[0] / med, 4), round(d[-1] / med, 4)],
+            "GiB_per_s": round(total / med / 2**30, 2)}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hash_chain", "bench.json"))
+    ap.add_argument("--seconds", type=float, default=1.0, help="device-timed work per path and shape")
+    ap.add_argument("--shapes", default="0,1,2,3,4")
+    args = ap.parse_args()
+    chosen = {int(x) for x in args.shapes.split(",")}
+
+    import torch
+
+    from efes_amd import _lib
+    from efes_amd.hashing import default_context, hash_chain_scratch
+
+    FIN, INIT, CHAIN = _lib.EFES_JOB_FINALIZE, _lib.EFES_JOB_INIT, _lib.EFES_JOB_CHAIN
+    ctx = default_context(0)
+    stream = torch.cuda.Stream(device="cuda:0")
+    s = stream.cuda_stream
+    buf = torch.empty(POOL, dtype=torch.uint8, device="cuda:0")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    log = open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "bench.log"), "w")
+    results = []
+    for si, (name, make) in enumerate(SHAPES):
+        if si not in chosen:
+            continue
+        objects = make()
+        nobj = len(objects)
+        counts = np.array([len(o) for o in objects], dtype=np.int64)
+        n, steps = int(counts.sum()), int(counts.max())
+        total = int(sum(m for o in objects for _, m in o))
+        owner = np.repeat(np.arange(nobj, dtype=np.uint64), counts)
+        step = np.concatenate([np.arange(c, dtype=np.int64) for c in counts])
+        ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
+        last = step == counts[owner.astype(np.int64)] - 1
+        with torch.cuda.stream(stream):
+            ctx.fill_synthetic(buf.data_ptr(), POOL, 0x5A1C + si, s)
+            res = {p: dict(states=torch.zeros(nobj * 104, dtype=torch.uint8, device="cuda:0"),
+                           crcs=torch.zeros(nobj, dtype=torch.int32, device="cuda:0"),
+                           sums=torch.zeros(nobj * 24, dtype=torch.uint8, device="cuda:0"),
+                           status=torch.full((n,), -99, dtype=torch.int32, device="cuda:0")) for p in ("chain", "steps", "steps-deep")}
+
+            def job_array(r, order, chained):
+                j = np.zeros(n, dtype=_lib.JOB_DTYPE)
+                j["data"] = np.uint64(buf.data_ptr()) + ext[:, 0]
+                j["length"] = ext[:, 1]
+                j["sha1"] = np.uint64(r["states"].data_ptr()) + owner * np.uint64(104)
+                j["crc32"] = np.uint64(r["crcs"].data_ptr()) + owner * np.uint64(4)
+                j["sum"] = np.uint64(r["sums"].data_ptr()) + owner * np.uint64(24)  # FINALIZE on the last extent only
+                j["status"] = np.uint64(r["status"].data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(4)
+                j["flags"] = np.where(step == 0, INIT, CHAIN if chained else 0).astype(np.uint32) | np.where(last, FIN, 0).astype(np.uint32)
+                return torch.from_numpy(j[order].view(np.uint8).copy()).to("cuda:0")
+
+            by_step = np.argsort(step, kind="stable")  # step after step, the objects in their order within each
+            first_of_step = np.searchsorted(step[by_step], np.arange(steps + 1))
+            chain_jobs = job_array(res["chain"], np.arange(n), True)
+            step_jobs = {p: job_array(res[p], by_step, False) for p in ("steps", "steps-deep")}
+            scratch = torch.empty(hash_chain_scratch(n), dtype=torch.uint8, device="cuda:0")
+        stream.synchronize()
+
+        def run_chain():
+            ctx.hash_chain(chain_jobs.data_ptr(), n, scratch.data_ptr(), scratch.numel(), s)
+
+        def run_steps(p, mode):
+            base = step_jobs[p].data_ptr()
+            for k in range(steps):
+                a, b = int(first_of_step[k]), int(first_of_step[k + 1])
+                ctx.submit(base + 56 * a, b - a, s, mode)
+
+        paths = {"chain": run_chain, "steps": lambda: run_steps("steps", _lib.MODE_AUTO),
+                 "steps-deep": lambda: run_steps("steps-deep", _lib.MODE_DEEP)}
+        dev = {p: [] for p in paths}
+        with torch.cuda.stream(stream):
+            for rep in range(20000):
+                todo = [p for p in paths if rep < 2 or sum(dev[p][1:]) < args.seconds]
+                if not todo:
+                    break
+                for p in todo:  # alternating; repetition 0 is the warm-up
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    paths[p]()
+                    e1.record(stream)
+                    stream.synchronize()
+                    dev[p].append(e0.elapsed_time(e1) / 1e3)
+        stream.synchronize()
+        # ---- correctness before any rate
+        sums = {p: res[p]["sums"].cpu().numpy().reshape(nobj, 24) for p in paths}
+        for p in paths:
+            assert (res[p]["status"].cpu().numpy() == 0).all(), (name, p)
+            assert (sums[p] == sums["chain"]).all(), (name, p, np.nonzero((sums[p] != sums["chain"]).any(axis=1))[0][:5])
+            assert (res[p]["crcs"].cpu().numpy() == res["chain"]["crcs"].cpu().numpy()).all(), (name, p)
+        for i in {0, nobj - 1}:
+            data = b"".join(bytes(buf[a:a + m].cpu().numpy()) for a, m in objects[i])
+            want = hashlib.sha1(data).digest() + zlib.crc32(data).to_bytes(4, "big")
+            assert bytes(sums["chain"][i]) == want, (name, i)
+        row = {"shape": name, "objects": nobj, "jobs": n, "extent_steps": steps, "bytes": total,
+               "longest_object_bytes": int(max(sum(m for _, m in o) for o in objects)),
+               "paths": {p: stats(total, dev[p]) for p in paths}}
+        a = row["paths"]["chain"]["device_seconds_median"]
+        row["chain_over_steps"] = round(a / row["paths"]["steps"]["device_seconds_median"], 4)
+        row["chain_over_steps_deep"] = round(a / row["paths"]["steps-deep"]["device_seconds_median"], 4)
+        results.append(row)
+        for f in (sys.stdout, log):
+            print(json.dumps(row), file=f, flush=True)
+    out = {"tool": "tools/bench_hash_chain.py", "device": torch.cuda.get_device_name(0), "build_id": _lib.lib().efes_build_id().decode(),
+           "pool_bytes": POOL, "seconds_per_path": args.seconds,
+           "checks": "every status EFES_OK; all paths' object sums and CRC states equal; two objects per shape equal hashlib and zlib",
+           "shapes": results}
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    log.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
