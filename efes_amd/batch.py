@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context, hash_chain_scratch
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context, hash_chain_auto_mode, hash_chain_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -226,17 +226,24 @@ class DeviceObjects:
     through efes_hash_chain, one wavefront per object: fused with crc32=True, SHA-1 alone with
     crc32=False.  Then sha1_hex() is the Sum at each object's last extent, running_sha1() the Sum at
     every extent's end (running=True) and states_host() the states, stale tail bytes included.
+
+    walk (sha1=True only) chooses how efes_hash_chain walks the objects: None is efes_hash_chain itself,
+    one wavefront per object; "auto" is efes_hash_chain_mode at the mode efes_hash_chain_auto_mode gives
+    for the number of objects that have extents (the grouped walk beyond one object per SIMD); an
+    EFES_MODE_* constant is passed to efes_hash_chain_mode as it is.  The results are the same bytes.
     """
 
     _ordered = DeviceBatch._ordered
 
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
-                 crc32: bool = True, states: np.ndarray | None = None):
+                 crc32: bool = True, states: np.ndarray | None = None, walk=None):
         import torch
 
         if not (sha1 or crc32):
             raise ValueError("DeviceObjects: sha1 or crc32 (or both)")
+        if walk is not None and not sha1:
+            raise ValueError("DeviceObjects: walk= needs sha1=True")
         if states is not None and not sha1:
             raise ValueError("DeviceObjects: states= needs sha1=True")
         self.has_sha1, self.has_crc32 = bool(sha1), bool(crc32)
@@ -280,6 +287,7 @@ class DeviceObjects:
         else:
             jobs["flags"][self.last[counts > 0]] |= EFES_JOB_FINALIZE
         self.running = bool(running)
+        self.walk = hash_chain_auto_mode(int((counts > 0).sum()), self.ctx) if walk == "auto" else walk
         self.jobs_host = jobs
         self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
         # allocated once and kept: one object set's launches run in stream order
@@ -295,6 +303,10 @@ class DeviceObjects:
                 self.states.copy_(self._init_states_dev)
 
     def submit(self) -> None:
+        if self.walk is not None:
+            self._ordered(lambda stream: self.ctx.hash_chain_mode(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
+                                                                  self._scratch.numel(), stream, self.walk))
+            return
         call = self.ctx.hash_chain if self.has_sha1 else self.ctx.crc32_chain
         self._ordered(lambda stream: call(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
                                           self._scratch.numel(), stream))

@@ -389,6 +389,31 @@ int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* s
   return hip_err(efes::launch_hash_chain(jobs, njobs, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
 }
 
+int efes_hash_chain_auto_mode(const efes_ctx* ctx, uint32_t nchains) {
+  // The wave walk up to one chain per SIMD; beyond, the most lanes per chain (the lowest per-block
+  // latency, 410 + ~700/G instructions) whose 64/G slots per SIMD still hold every chain at once.
+  const uint64_t simds = 4ull * (ctx ? (uint64_t)ctx->cus : 256ull), n = nchains;
+  if (n <= simds) return EFES_MODE_DEEP;
+  if (n <= 2 * simds) return EFES_MODE_GROUP32;
+  if (n <= 4 * simds) return EFES_MODE_GROUP16;
+  if (n <= 8 * simds) return EFES_MODE_GROUP8;
+  return EFES_MODE_GROUP4;
+}
+
+int efes_hash_chain_mode(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* scratch, size_t scratch_bytes,
+                         void* stream, int mode) {
+  const int lanes = efes::group_of_mode(mode);
+  if (mode != EFES_MODE_DEEP && !lanes) return EFES_ERR_ARG;  // AUTO too: the chain count lives on the device
+  if (!lanes) return efes_hash_chain(ctx, jobs, njobs, scratch, scratch_bytes, stream);
+  if (!ctx || (!jobs && njobs) || njobs > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::hash_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(
+      efes::launch_hash_chain_group(jobs, njobs, lanes, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
+}
+
 int efes_crc32_tables(uint32_t* out, size_t nwords) {
   const size_t need = sizeof(Tables) / 4, with_pos = need + sizeof(efes::PosTables) / 4;
   if (!out || nwords < need) return EFES_ERR_ARG;

@@ -162,6 +162,10 @@ hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch,
 size_t hash_chain_scratch_bytes(uint32_t njobs);
 hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs, int cus,
                              hipStream_t s);
+// The grouped walk (efes_hash_chain_mode): the same prep launches and scratch, then a persistent launch
+// in which each wavefront holds 64/G chains at once, G in {4, 8, 16, 32}, and advances them together.
+hipError_t launch_hash_chain_group(const efes_job* jobs, uint32_t njobs, int G, void* scratch, const Tables* tabs,
+                                   int cus, hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

@@ -651,7 +651,9 @@ __device__ __forceinline__ uint32_t crc_block_pos(const uint32_t (&pos)[64][256]
 
 // kSha / kCrc are wave-uniform (any joining job needs the hash): with both, the CRC lookups and
 // the schedule expansion share one basic block, so the lookups' latency hides behind VALU work.
-template <int G, bool kAligned16, bool kSha, bool kCrc>
+// kUser: the kernel that calls it (0 group_kernel, 1 hash_chain_group_kernel), so that each has an
+// instantiation of its own, with one call site, and compiles as if the other did not exist.
+template <int G, bool kAligned16, bool kSha, bool kCrc, int kUser = 0>
 __device__ void group_bulk(const Tables& T, const PosTables& P, int lane, DeepMsg* msgs, uint64_t S) {
   constexpr int kLG = G == 4 ? 2 : G == 8 ? 3 : G == 16 ? 4 : 5;
   static_assert((1 << kLG) == G, "G must be 4, 8, 16 or 32");
@@ -720,12 +722,12 @@ __device__ void group_bulk(const Tables& T, const PosTables& P, int lane, DeepMs
   wave_lds_sync();
 }
 
-template <int G, bool kAligned16>
+template <int G, bool kAligned16, int kUser = 0>
 __device__ void group_bulk_any(const Tables& T, const PosTables& P, int lane, DeepMsg* msgs, uint64_t S, bool any_sha,
                                bool any_crc) {
-  if (any_sha && any_crc) group_bulk<G, kAligned16, true, true>(T, P, lane, msgs, S);
-  else if (any_sha) group_bulk<G, kAligned16, true, false>(T, P, lane, msgs, S);
-  else group_bulk<G, kAligned16, false, true>(T, P, lane, msgs, S);
+  if (any_sha && any_crc) group_bulk<G, kAligned16, true, true, kUser>(T, P, lane, msgs, S);
+  else if (any_sha) group_bulk<G, kAligned16, true, false, kUser>(T, P, lane, msgs, S);
+  else group_bulk<G, kAligned16, false, true, kUser>(T, P, lane, msgs, S);
 }
 
 
@@ -1818,17 +1820,22 @@ size_t hash_chain_scratch_bytes(uint32_t njobs) {
   return (b + 15) & ~(size_t)15;
 }
 
-hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs, int cus,
-                             hipStream_t s) {
-  if (njobs == 0) return hipSuccess;
+// The two prep launches: the chains' heads listed in the scratch, the ticket zeroed.
+static hipError_t launch_hash_chain_prep(const efes_job* jobs, uint32_t njobs, void* scratch, hipStream_t s) {
   const uint32_t nblocks = (njobs + kChainBlock - 1) / kChainBlock;
   clear_last_error();
   hipLaunchKernelGGL(hash_chain_mark_kernel, dim3(nblocks), dim3(kChainBlock), 0, s, jobs, njobs, scratch);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   clear_last_error();
   hipLaunchKernelGGL(hash_chain_list_kernel, dim3(nblocks), dim3(kChainBlock), 0, s, jobs, njobs, scratch);
-  e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs, int cus,
+                             hipStream_t s) {
+  if (njobs == 0) return hipSuccess;
+  const hipError_t e = launch_hash_chain_prep(jobs, njobs, scratch, s);
   if (e != hipSuccess) return e;
   // Persistent grid: the chain count lives on the device, so the grid is sized by the job count and
   // by what is resident at once (a workgroup that starts late finds the tickets gone and leaves).
@@ -1842,6 +1849,221 @@ hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch
   hipLaunchKernelGGL(hash_chain_kernel, dim3((uint32_t)std::min(want, resident)), dim3(64 * kDeepWaves), 0, s, jobs,
                      njobs, tabs, scratch);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ grouped walk (efes_hash_chain_mode)
+// For more chains than SIMDs: the same prep launches, scratch, ticket and heads[] list, then a persistent
+// launch of group_kernel's workgroup (four waves, one per SIMD; Tables + PosTables, msg, xs and fin in
+// LDS, over half a CU's LDS, so a workgroup owns its CU).  A wave has 64/G slots and each slot holds one
+// chain: its ticket range [cur, end), the validity state the wave walk keeps, and the DeepMsg of its
+// current member.  The wave alternates two steps, all of it wave-uniform:
+//   1. refill: every slot without a joinable member (>= G bulk blocks left) is driven on -- a headed
+//      member with fewer than G blocks left is finished by deep_rest<true>, the cursor advances, at a
+//      chain's end the slot draws the next chain (one atomic add by lane 0, broadcast; the wave's first
+//      64/G tickets come from one add; a spent ticket leaves the slot dead: DeepMsg{}), each new member
+//      is checked by the wave walk's rules (invalid: EFES_ERR_ARG and nothing else) and gets deep_head
+//      into the slot's xs.  The wave walk's drain and agent-scope fence stand before every deep_head
+//      that follows a deep_rest of this wave.
+//   2. joint round: with no joiner the wave leaves; a lone joiner (every other slot is then dead) goes
+//      back through step 1, which finishes it on the one-job path; two or more advance together by S*G
+//      blocks through group_bulk_any, S the smallest left/G among them, then step 1 again.
+// No wave waits for another; every loop bound comes from memory an earlier launch wrote, or from the
+// ticket.  No LDS-DMA; the only inline assembly is the wave walk's wait.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   hash_chain_group_kernel<4>    215 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 52 SGPRs kept in VGPR lanes
+//   hash_chain_group_kernel<8>    215 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 49 SGPRs kept in VGPR lanes
+//   hash_chain_group_kernel<16>   215 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 51 SGPRs kept in VGPR lanes
+//   hash_chain_group_kernel<32>   217 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 53 SGPRs kept in VGPR lanes
+//   each 1 wave/SIMD (one workgroup per CU, by LDS), no AGPRs.
+// deep_kernel, group_kernel<*>, fed_kernel<*>, wide_kernel and hash_chain_kernel compile to the same
+// registers, LDS, scratch and occupancy with and without this section.  That needs group_bulk's kUser: with
+// a second caller of one instantiation the compiler stops inlining it into group_kernel as well (248 VGPRs
+// + 32 AGPRs, 180-260 B of scratch per lane in both kernels).
+struct ChainSlot {
+  uint32_t cur, end;    // the chain's members not yet finished: jobs [cur, end)
+  uint32_t first;       // the chain's head
+  uint32_t bad;         // an invalid member was met: the members behind it are invalid too
+  uint32_t prev_flags;  // the valid member before: its flags and the states it names
+  uint32_t pad;
+  const efes_sha1_state* prev_st;
+  const efes_crc32_state* prev_cs;
+};
+struct ChainGroupLDS {
+  DeepLDS d;
+  ChainSlot slot[kDeepWaves][kGroupMaxJobs];
+};
+static_assert(sizeof(ChainGroupLDS) > kCuLds / 2 && sizeof(ChainGroupLDS) <= kCuLds, "one workgroup per CU");
+
+template <int G>
+__global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(const efes_job* __restrict__ jobs,
+                                                                              uint32_t njobs,
+                                                                              const Tables* __restrict__ tabs,
+                                                                              void* scratch) {
+  constexpr int kSlots = 64 / G;
+  static_assert(kSlots <= kGroupMaxJobs, "LDS holds kGroupMaxJobs slots per wave");
+  __shared__ __attribute__((aligned(16))) ChainGroupLDS L;
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(tabs);  // Tables then PosTables
+    uint4* dst = reinterpret_cast<uint4*>(&L.d.tab);
+    for (int i = threadIdx.x; i < (int)((sizeof(Tables) + sizeof(PosTables)) / 16); i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int wave = (int)uniform32(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const HashChainScratch S = hash_chain_scratch_of(scratch, njobs);
+  const uint32_t count = uniform32(S.ctl->count);
+  DeepMsg* msgs = L.d.msg[wave];
+  ChainSlot* slots = L.slot[wave];
+  if (lane < kSlots) {
+    msgs[lane] = DeepMsg{};
+    slots[lane] = ChainSlot{};
+  }
+  wave_lds_sync();
+  // A wave's first draw is one atomic add for all its slots, so that it starts with consecutive chains
+  // (of similar lengths in an array sorted longest first, as the grouped job kernels expect) and two
+  // chains of a small array meet in one wave; every later draw is one ticket for one slot.
+  uint32_t pre = 0;
+  if (lane == 0) pre = atomicAdd(&S.ctl->ticket, (uint32_t)kSlots);
+  pre = uniform32(pre);
+  const uint32_t pre_end = pre + (uint32_t)kSlots;
+  bool spent = false;  // the ticket has reached the count: no slot of this wave draws again
+  bool wrote = false;  // a deep_rest of this wave stored a state since the last fence
+  int lone = -1;       // the slot whose member was left alone by the last step 2
+  for (;;) {
+    // ---- step 1: refill
+    for (int m = 0; m < kSlots; ++m) {
+      const bool live0 = uniform32(msgs[m].live) != 0u;
+      if (live0 && m != lone && uniform64(msgs[m].nbulk) - uniform64(msgs[m].done) >= (uint64_t)G) continue;
+      ChainSlot C;
+      C.cur = uniform32(slots[m].cur);
+      C.end = uniform32(slots[m].end);
+      if (!live0 && spent && C.cur >= C.end) continue;  // dead
+      C.first = uniform32(slots[m].first);
+      C.bad = uniform32(slots[m].bad);
+      C.prev_flags = uniform32(slots[m].prev_flags);
+      C.pad = 0;
+      C.prev_st = reinterpret_cast<const efes_sha1_state*>(uniform64(reinterpret_cast<uint64_t>(slots[m].prev_st)));
+      C.prev_cs = reinterpret_cast<const efes_crc32_state*>(uniform64(reinterpret_cast<uint64_t>(slots[m].prev_cs)));
+      DeepMsg M = uniform_msg(msgs[m]);
+      for (;;) {
+        if (M.live) {
+          if (m != lone && M.nbulk - M.done >= (uint64_t)G) break;  // joinable
+          deep_rest<true>(L.d.tab, lane, load_job(jobs, C.cur, lane), L.d.xs[wave][m], L.d.fin[wave], M);
+          wrote = true;
+          M = DeepMsg{};
+          ++C.cur;
+        }
+        if (C.cur >= C.end) {  // the chain's end: the next chain
+          uint32_t t = 0;
+          if (!spent) {
+            if (pre < pre_end) {
+              t = pre++;
+            } else {
+              if (lane == 0) t = atomicAdd(&S.ctl->ticket, 1u);
+              t = uniform32(t);
+            }
+            spent = t >= count;
+          }
+          if (spent) break;  // dead: M is DeepMsg{}
+          C.first = uniform32(S.heads[t]);
+          uint32_t end = njobs;
+          if (t + 1u < count) end = uniform32(S.heads[t + 1u]);
+          C.end = end < njobs ? end : njobs;
+          C.cur = C.first;
+          C.bad = 0u;
+          C.prev_flags = 0u;
+          C.prev_st = nullptr;
+          C.prev_cs = nullptr;
+          if (C.cur >= C.end) continue;
+        }
+        const DeepJob J = load_job(jobs, C.cur, lane);
+        if (J.flags & EFES_JOB_CHAIN)  // cur == first: job 0, a follower of nothing
+          C.bad |= (C.cur == C.first || J.st != C.prev_st || J.cs != C.prev_cs || (J.st == nullptr && J.cs == nullptr) ||
+                    (J.flags & (EFES_JOB_INIT | EFES_JOB_SUM_ONLY)) != 0u || (C.prev_flags & EFES_JOB_SUM_ONLY) != 0u)
+                       ? 1u
+                       : 0u;
+        if (C.bad) {  // not a Write into its chain's state: reported, nothing of it touched
+          if (lane == 0 && J.status) *J.status = EFES_ERR_ARG;
+          ++C.cur;
+          continue;
+        }
+        if (wrote) {  // a member before stored the state this one may load
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          wrote = false;
+        }
+        M = deep_head(L.d.tab, lane, J, L.d.xs[wave][m]);
+        C.prev_st = J.st;
+        C.prev_cs = J.cs;
+        C.prev_flags = J.flags;
+        if (!M.live) ++C.cur;  // Go panicked at the Write: the status is written, nothing else
+      }
+      wave_lds_sync();
+      if (lane == 0) {
+        msgs[m] = M;
+        slots[m] = C;
+      }
+    }
+    lone = -1;
+    wave_lds_sync();
+
+    // ---- step 2: joint round of the slots whose member has >= G bulk blocks left
+    uint64_t St = ~0ull;
+    int joiners = 0;
+    bool any_sha = false, any_crc = false, all16 = true;
+    for (int m = 0; m < kSlots; ++m) {
+      const uint64_t left = uniform32(msgs[m].live) ? (uniform64(msgs[m].nbulk) - uniform64(msgs[m].done)) / G : 0;
+      if (lane == 0) msgs[m].joint = left ? 1u : 0u;
+      if (left == 0) continue;
+      ++joiners;
+      lone = m;
+      St = left < St ? left : St;
+      const DeepJob J = load_job(jobs, uniform32(slots[m].cur), lane);
+      any_sha |= J.st != nullptr;
+      any_crc |= J.cs != nullptr;
+      const uint8_t* q = reinterpret_cast<const uint8_t*>(uniform64(reinterpret_cast<uint64_t>(msgs[m].q)));
+      all16 &= (reinterpret_cast<uintptr_t>(q + 64 * uniform64(msgs[m].done)) & 15) == 0;
+    }
+    if (joiners == 0) break;
+    if (joiners == 1) continue;  // step 1 runs slot `lone` to its member's end on the one-job path
+    lone = -1;
+    wave_lds_sync();
+    if (all16) group_bulk_any<G, true, 1>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
+    else group_bulk_any<G, false, 1>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
+  }
+}
+
+template <int G>
+hipError_t launch_hash_chain_group_shape(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                                         int cus, hipStream_t s) {
+  // Persistent grid, as the wave walk's: the workgroups that njobs chains would fill, or what is resident.
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hash_chain_group_kernel<G>, 64 * kDeepWaves, 0) !=
+          hipSuccess ||
+      per_cu < 1)
+    per_cu = 1;
+  const uint64_t resident = (uint64_t)(cus > 0 ? cus : 256) * (uint64_t)per_cu;
+  const uint64_t per_block = (uint64_t)kDeepWaves * (64 / G);
+  const uint64_t want = ((uint64_t)njobs + per_block - 1) / per_block;
+  clear_last_error();
+  hipLaunchKernelGGL(hash_chain_group_kernel<G>, dim3((uint32_t)std::min(want, resident)), dim3(64 * kDeepWaves), 0, s,
+                     jobs, njobs, tabs, scratch);
+  return hipGetLastError();
+}
+
+hipError_t launch_hash_chain_group(const efes_job* jobs, uint32_t njobs, int G, void* scratch, const Tables* tabs,
+                                   int cus, hipStream_t s) {
+  if (njobs == 0) return hipSuccess;
+  if (G != 4 && G != 8 && G != 16 && G != 32) return hipErrorInvalidValue;
+  const hipError_t e = launch_hash_chain_prep(jobs, njobs, scratch, s);
+  if (e != hipSuccess) return e;
+  switch (G) {
+    case 4: return launch_hash_chain_group_shape<4>(jobs, njobs, scratch, tabs, cus, s);
+    case 8: return launch_hash_chain_group_shape<8>(jobs, njobs, scratch, tabs, cus, s);
+    case 16: return launch_hash_chain_group_shape<16>(jobs, njobs, scratch, tabs, cus, s);
+    default: return launch_hash_chain_group_shape<32>(jobs, njobs, scratch, tabs, cus, s);
+  }
 }
 
 }  // namespace efes

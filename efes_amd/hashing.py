@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "hash_chain_scratch", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -59,6 +59,13 @@ def hash_chain_scratch(n: int) -> int:
     """efes_hash_chain_scratch: device bytes efes_hash_chain needs for n jobs (0 for n == 0 or more than
     EFES_HASH_CHAIN_MAX_JOBS)."""
     return int(lib().efes_hash_chain_scratch(n))
+
+
+def hash_chain_auto_mode(nchains: int, ctx: "Context | None" = None) -> int:
+    """efes_hash_chain_auto_mode: the mode for hash_chain_mode() when nchains objects are walked at once
+    (host-only; without a context one MI355X is assumed): MODE_DEEP up to one chain per SIMD, then the
+    grouped walk with as many lanes per chain as still hold every chain at once."""
+    return int(lib().efes_hash_chain_auto_mode(ctx.handle if ctx else None, nchains))
 
 
 class Context:
@@ -118,6 +125,15 @@ class Context:
         each chain, so an object in many extents takes one call; scratch: hash_chain_scratch(njobs) device
         bytes, 16-byte aligned, one buffer per call that may overlap another (asynchronous on `stream`)."""
         check(lib().efes_hash_chain(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_hash_chain")
+
+    def hash_chain_mode(self, jobs_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
+                        stream: int | None, mode: int) -> None:
+        """efes_hash_chain_mode: hash_chain() with the walk chosen by the caller -- MODE_DEEP is the wave
+        walk of hash_chain(), MODE_GROUP[G] the grouped walk with 64/G chains per wavefront, for more
+        chains than SIMDs (hash_chain_auto_mode(nchains) picks one).  The same bytes either way; no
+        MODE_AUTO, since the chain count lives on the device."""
+        check(lib().efes_hash_chain_mode(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream, mode),
+              "efes_hash_chain_mode")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

@@ -94,7 +94,7 @@ void* efes_ctx_stream(efes_ctx* ctx);
 #define EFES_JOB_SUM_ONLY 0x4u /* with EFES_JOB_FINALIZE and length 0: Sum of the in-state on a copy
                                   (sha1.go:82-87 `d0 := *d`): the states are read, never written, so
                                   a pending full tail (nx == 64) stays pending as in Go */
-#define EFES_JOB_CHAIN 0x8u    /* efes_crc32_chain and efes_hash_chain only: this job is the next Write into
+#define EFES_JOB_CHAIN 0x8u    /* efes_crc32_chain and efes_hash_chain(_mode) only: this job is the next Write into
                                   the state(s) of the job before it (below); every other call ignores the bit */
 
 /* One `Write(p)` (+ optional Sum) of len(p) = length bytes at device address `data`.
@@ -506,24 +506,53 @@ int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs,
  * DEEP shape, so a call lasts as long as its longest chains, not as the sum over extent steps of the
  * longest extent in each (DESIGN.md §4 "Chained SHA-1 + CRC").  EFES_ABI_VERSION stays 8: the addition
  * changes nothing that existed, and a binding detects it by the symbol.
- * Which path when (measured, profiles/hash_chain/bench.json; DESIGN.md §4 "Chained SHA-1 + CRC" has the
- * table; "steps" = one efes_hash_submit per extent step on one stream, one job per object that still has
- * an extent, AUTO or forced DEEP):
+ * Which path when (measured, profiles/hash_chain_group/bench.json; DESIGN.md §4 "Chained SHA-1 + CRC,
+ * grouped walk" has the table; "steps" = one efes_hash_submit per extent step on one stream, one job per
+ * object that still has an extent, AUTO or forced DEEP; "grouped walk" = efes_hash_chain_mode at the mode
+ * efes_hash_chain_auto_mode gives for the object count, declared below):
  *   - objects of UNEQUAL extent counts or sizes, no more of them than SIMDs (1024 objects of 1-64 extents
  *     of 4 KiB-1 MiB, longest first): efes_hash_chain.  It takes about 0.6 of the steps' device time: the
  *     longest object's own chain instead of the sum over steps of the longest extent in each;
  *   - objects of EQUAL extents, no more of them than SIMDs (1024 objects x 16 x 256 KiB, x 128 x 32 KiB):
  *     either.  On the device the chain call takes 3 to 4 % and 2 % longer than the steps -- its waves
  *     run without DEEP's producer wave -- and is one call instead of 16 or 128;
- *   - more objects than SIMDs (4096 objects x 16 x 64 KiB): the steps through efes_hash_submit (AUTO).
- *     The chain call runs one chain per SIMD at a time and takes about 3.8 times as long as AUTO's FED4
- *     launches there (2 % longer than the steps forced to DEEP);
+ *   - more objects than SIMDs, UNEQUAL extents (4096 objects of 1-16 extents of 4 KiB-256 KiB, longest
+ *     first): the grouped walk.  38 ms against 51 ms for the steps and 55 ms for efes_hash_chain;
+ *   - more objects than SIMDs, EQUAL extents (4096 objects x 16 x 64 KiB; 16 384 x 4 x 64 KiB): the
+ *     grouped walk as ONE call, at 0.29 and 0.11 of efes_hash_chain's time; the steps through
+ *     efes_hash_submit (AUTO) where 16 or 4 calls are no burden: they stay 1.14 and 1.21 times faster
+ *     than the grouped walk (FED4's producer SIMDs at 4096; four GROUP4 launches without the per-member
+ *     refill at 16 384).  efes_hash_chain itself runs one chain per SIMD at a time there: 3.9 and 10.8
+ *     times the steps' time.  A forced EFES_MODE_GROUP4 at 4096 objects takes 1.25 times GROUP16's time;
  *   - an array without EFES_JOB_CHAIN (1024 x 4 MiB): efes_hash_submit; the chain call takes 3 to 4 %
  *     longer than EFES_MODE_DEEP for the same bytes. */
 #define EFES_HASH_CHAIN_MAX_JOBS (1u << 20)
 size_t efes_hash_chain_scratch(uint32_t njobs);
 int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
                     size_t scratch_bytes, void* stream);
+
+/* efes_hash_chain with the walk chosen by the caller.  Everything efes_hash_chain takes, and its whole
+ * contract: the job array, the chain and validity rules, the statuses, the final states with their stale
+ * bytes x[nx:64], the per-member sums, the argument errors, the scratch (efes_hash_chain_scratch(njobs)),
+ * no host read-back, allocation or wait.  For every job array and every accepted mode it writes byte for
+ * byte what efes_hash_chain writes; the yardstick stays Go's Write; Write; ....
+ *   - EFES_MODE_DEEP: the wave walk, the very launches of efes_hash_chain (one chain per wavefront);
+ *   - EFES_MODE_GROUP4 / GROUP8 / GROUP16 / GROUP32: the grouped walk for more chains than SIMDs.  A
+ *     wavefront holds 64/G chains at once, G lanes each, and advances those whose current member has at
+ *     least G whole blocks left together, as the grouped job kernels advance jobs (410 + ~700/G
+ *     instructions per block and chain); heads, tails, Sums and members shorter than G blocks go through
+ *     the one-wave path, one at a time.  A slot whose chain ends draws the next chain, so chains of
+ *     unequal extent counts and sizes keep the wavefront full;
+ *   - every other value, EFES_MODE_AUTO included, returns EFES_ERR_ARG: the chain count lives on the
+ *     device and the call reads nothing back.
+ * efes_hash_chain_auto_mode (host-only; ctx may be NULL: 256 CUs) gives the mode for a caller that knows
+ * how many chains (objects) the array holds: EFES_MODE_DEEP up to one chain per SIMD, else the largest G
+ * whose 64/G chains per SIMD still hold every chain at once -- GROUP32 up to 2 per SIMD, GROUP16 up to 4,
+ * GROUP8 up to 8 -- and GROUP4 beyond.
+ * EFES_ABI_VERSION stays 8; a binding detects the two calls by their symbols. */
+int efes_hash_chain_mode(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
+                         size_t scratch_bytes, void* stream, int mode);
+int efes_hash_chain_auto_mode(const efes_ctx* ctx, uint32_t nchains);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 

@@ -1,7 +1,8 @@
 """Chained SHA-1 + CRC-32 jobs against what a caller had before, in one GPU run: writes
-profiles/hash_chain/bench.json and bench.log beside it.
+profiles/hash_chain_group/bench.json and bench.log beside it (profiles/hash_chain/ holds the run from
+before the grouped walk, paths (a) to (c)).
 
-    python tools/bench_hash_chain.py [--out PATH] [--seconds 1.0] [--shapes 0,1,2,3,4]
+    python tools/bench_hash_chain.py [--out PATH] [--seconds 1.0] [--shapes 0,1,2,3,4,5,6]
 
 Synthetic bytes in a 4 GiB pool (well past the 256 MiB Infinity Cache), fused jobs, every repetition from
 NewSha1() / NewCRC32IEEE().  The paths alternate in this process, each warmed once and then repeated until
@@ -9,11 +10,16 @@ its device-event-timed work reaches --seconds:
   (a) chain -- one efes_hash_chain call over all extents, one state pair per object;
   (b) steps -- what a caller does without it: one efes_hash_submit (AUTO) per extent step on one stream,
       with one job per object that still has an extent;
-  (c) steps-deep -- the same launches forced to EFES_MODE_DEEP.
+  (c) steps-deep -- the same launches forced to EFES_MODE_DEEP;
+  (d) group -- one efes_hash_chain_mode call at the mode efes_hash_chain_auto_mode gives for the object
+      count (EFES_MODE_DEEP up to one object per SIMD: then the wave walk's launches, a second sample of (a));
+  (e) group4 -- the 4096-object shape only: the same call forced to EFES_MODE_GROUP4, so that the choice of
+      G is seen and not assumed.
 Shapes: 1024 objects x 16 extents x 256 KiB (a 4 MiB PATCH in staging chunks); 1024 x 128 x 32 KiB
 (io.Copy-sized Writes); a seeded ragged set, 1024 objects of 1-64 extents of 4 KiB-1 MiB, longest object
 first; 4096 x 16 x 64 KiB (more chains than SIMDs); 1024 x 4 MiB with no job flagged, where (b) and (c) are
-one efes_hash_submit(AUTO) / efes_hash_submit_mode(DEEP) of the same array.
+one efes_hash_submit(AUTO) / efes_hash_submit_mode(DEEP) of the same array; 16 384 x 4 x 64 KiB; and a
+seeded ragged set of 4096 objects of 1-16 extents of 4 KiB-256 KiB, longest object first.
 Before any rate is printed every path's status must be EFES_OK, the objects' 24-byte sums of all paths
 must be equal, and two objects per shape must match hashlib and zlib.
 """
@@ -41,14 +47,15 @@ def equal_shape(nobj: int, next_: int, size: int):
     return [[((i * next_ + k) * size, size) for k in range(next_)] for i in range(nobj)]
 
 
-def ragged_shape(seed: int = 0x4A66ED):
-    """1024 objects of 1-64 extents of 4 KiB-1 MiB at seeded 4 KiB-aligned pool offsets, longest object first."""
+def ragged_shape(seed: int = 0x4A66ED, nobj: int = 1024, max_extents: int = 64, max_size: int = 1 << 20):
+    """nobj objects of 1-max_extents extents of 4 KiB-max_size at seeded 4 KiB-aligned pool offsets, longest
+    object first."""
     rng = np.random.default_rng(seed)
     objects = []
-    for _ in range(1024):
-        k = int(rng.integers(1, 65))
-        lens = rng.integers(4 << 10, (1 << 20) + 1, size=k)
-        offs = rng.integers(0, (POOL - (1 << 20)) >> 12, size=k) << 12
+    for _ in range(nobj):
+        k = int(rng.integers(1, max_extents + 1))
+        lens = rng.integers(4 << 10, max_size + 1, size=k)
+        offs = rng.integers(0, (POOL - max_size) >> 12, size=k) << 12
         objects.append([(int(o), int(n)) for o, n in zip(offs, lens)])
     objects.sort(key=lambda o: -sum(n for _, n in o))
     return objects
@@ -58,7 +65,11 @@ SHAPES = [("1024 objects x 16 extents x 256 KiB", lambda: equal_shape(1024, 16, 
           ("1024 objects x 128 extents x 32 KiB", lambda: equal_shape(1024, 128, 32 << 10)),
           ("ragged: 1024 objects x 1-64 extents x 4 KiB-1 MiB, longest first", ragged_shape),
           ("4096 objects x 16 extents x 64 KiB", lambda: equal_shape(4096, 16, 64 << 10)),
-          ("1024 x 4 MiB, unflagged", lambda: equal_shape(1024, 1, 4 << 20))]
+          ("1024 x 4 MiB, unflagged", lambda: equal_shape(1024, 1, 4 << 20)),
+          ("16384 objects x 4 extents x 64 KiB", lambda: equal_shape(16384, 4, 64 << 10)),
+          ("ragged: 4096 objects x 1-16 extents x 4 KiB-256 KiB, longest first",
+           lambda: ragged_shape(0x4A66EE, 4096, 16, 256 << 10))]
+FORCED_GROUP4 = {3}  # shapes with column (e)
 
 
 def stats(total: int, dev: list[float]) -> dict:
@@ -72,16 +83,16 @@ def stats(total: int, dev: list[float]) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hash_chain", "bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hash_chain_group", "bench.json"))
     ap.add_argument("--seconds", type=float, default=1.0, help="device-timed work per path and shape")
-    ap.add_argument("--shapes", default="0,1,2,3,4")
+    ap.add_argument("--shapes", default="0,1,2,3,4,5,6")
     args = ap.parse_args()
     chosen = {int(x) for x in args.shapes.split(",")}
 
     import torch
 
     from efes_amd import _lib
-    from efes_amd.hashing import default_context, hash_chain_scratch
+    from efes_amd.hashing import default_context, hash_chain_auto_mode, hash_chain_scratch
 
     FIN, INIT, CHAIN = _lib.EFES_JOB_FINALIZE, _lib.EFES_JOB_INIT, _lib.EFES_JOB_CHAIN
     ctx = default_context(0)
@@ -103,12 +114,14 @@ def main() -> int:
         step = np.concatenate([np.arange(c, dtype=np.int64) for c in counts])
         ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
         last = step == counts[owner.astype(np.int64)] - 1
+        auto = hash_chain_auto_mode(nobj, ctx)
+        group_paths = {"group": auto, **({"group4": _lib.MODE_GROUP[4]} if si in FORCED_GROUP4 else {})}
         with torch.cuda.stream(stream):
             ctx.fill_synthetic(buf.data_ptr(), POOL, 0x5A1C + si, s)
             res = {p: dict(states=torch.zeros(nobj * 104, dtype=torch.uint8, device="cuda:0"),
                            crcs=torch.zeros(nobj, dtype=torch.int32, device="cuda:0"),
                            sums=torch.zeros(nobj * 24, dtype=torch.uint8, device="cuda:0"),
-                           status=torch.full((n,), -99, dtype=torch.int32, device="cuda:0")) for p in ("chain", "steps", "steps-deep")}
+                           status=torch.full((n,), -99, dtype=torch.int32, device="cuda:0")) for p in ("chain", "steps", "steps-deep", *group_paths)}
 
             def job_array(r, order, chained):
                 j = np.zeros(n, dtype=_lib.JOB_DTYPE)
@@ -124,12 +137,16 @@ def main() -> int:
             by_step = np.argsort(step, kind="stable")  # step after step, the objects in their order within each
             first_of_step = np.searchsorted(step[by_step], np.arange(steps + 1))
             chain_jobs = job_array(res["chain"], np.arange(n), True)
+            group_jobs = {p: job_array(res[p], np.arange(n), True) for p in group_paths}
             step_jobs = {p: job_array(res[p], by_step, False) for p in ("steps", "steps-deep")}
             scratch = torch.empty(hash_chain_scratch(n), dtype=torch.uint8, device="cuda:0")
         stream.synchronize()
 
         def run_chain():
             ctx.hash_chain(chain_jobs.data_ptr(), n, scratch.data_ptr(), scratch.numel(), s)
+
+        def run_group(p):
+            ctx.hash_chain_mode(group_jobs[p].data_ptr(), n, scratch.data_ptr(), scratch.numel(), s, group_paths[p])
 
         def run_steps(p, mode):
             base = step_jobs[p].data_ptr()
@@ -138,7 +155,8 @@ def main() -> int:
                 ctx.submit(base + 56 * a, b - a, s, mode)
 
         paths = {"chain": run_chain, "steps": lambda: run_steps("steps", _lib.MODE_AUTO),
-                 "steps-deep": lambda: run_steps("steps-deep", _lib.MODE_DEEP)}
+                 "steps-deep": lambda: run_steps("steps-deep", _lib.MODE_DEEP),
+                 **{p: (lambda p=p: run_group(p)) for p in group_paths}}
         dev = {p: [] for p in paths}
         with torch.cuda.stream(stream):
             for rep in range(20000):
@@ -166,10 +184,15 @@ def main() -> int:
             assert bytes(sums["chain"][i]) == want, (name, i)
         row = {"shape": name, "objects": nobj, "jobs": n, "extent_steps": steps, "bytes": total,
                "longest_object_bytes": int(max(sum(m for _, m in o) for o in objects)),
+               "group_mode": {v: k for k, v in {"DEEP": _lib.MODE_DEEP, **{"GROUP%d" % g: m for g, m in _lib.MODE_GROUP.items()}}.items()}[auto],
                "paths": {p: stats(total, dev[p]) for p in paths}}
         a = row["paths"]["chain"]["device_seconds_median"]
         row["chain_over_steps"] = round(a / row["paths"]["steps"]["device_seconds_median"], 4)
         row["chain_over_steps_deep"] = round(a / row["paths"]["steps-deep"]["device_seconds_median"], 4)
+        for p in group_paths:
+            d = row["paths"][p]["device_seconds_median"]
+            row[p + "_over_chain"] = round(d / a, 4)
+            row[p + "_over_steps"] = round(d / row["paths"]["steps"]["device_seconds_median"], 4)
         results.append(row)
         for f in (sys.stdout, log):
             print(json.dumps(row), file=f, flush=True)
