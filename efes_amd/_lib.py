@@ -176,6 +176,8 @@ SIGNATURES = {
     "efes_crc32_batch": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_crc32_chain_scratch": (_S, [_U32]),
     "efes_crc32_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
+    "efes_crc32_copy_scratch": (_S, [_U32]),
+    "efes_crc32_copy": (_I, [_VP, _VP, _VP, _U32, _VP, _S, _VP]),
     "efes_hash_chain_scratch": (_S, [_U32]),
     "efes_hash_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_hash_chain_mode": (_I, [_VP, _VP, _U32, _VP, _S, _VP, _I]),

@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, default_context, hash_chain_auto_mode, hash_chain_scratch
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -211,6 +211,22 @@ class DeviceBatch:
         return self.states.cpu().numpy().view(SHA1_STATE_DTYPE)[: self.n]
 
 
+COPY_ALIGN = 256  # DeviceObjects(copy_to=...): every object's start in the default layout
+
+
+def default_copy_offsets(objects) -> tuple[np.ndarray, int]:
+    """The default destination layout of DeviceObjects(copy_to=...): the objects back to back in their
+    order, every object's start rounded up to COPY_ALIGN bytes.  Host arithmetic over the extents'
+    lengths: (offset of each object, bytes of room the layout needs)."""
+    sizes = [sum(int(n) for _, n in o) for o in objects]
+    offsets, at = np.zeros(len(sizes), dtype=np.uint64), 0
+    for i, size in enumerate(sizes):
+        at = (at + COPY_ALIGN - 1) // COPY_ALIGN * COPY_ALIGN
+        offsets[i] = at
+        at += size
+    return offsets, at
+
+
 class DeviceObjects:
     """CRC-32 (and, with sha1=True, SHA-1) of objects that lie in many device extents, in one call:
     efes_crc32_chain for the default CRC-only set, efes_hash_chain for a set built with sha1=True.
@@ -231,13 +247,24 @@ class DeviceObjects:
     one wavefront per object; "auto" is efes_hash_chain_mode at the mode efes_hash_chain_auto_mode gives
     for the number of objects that have extents (the grouped walk beyond one object per SIMD); an
     EFES_MODE_* constant is passed to efes_hash_chain_mode as it is.  The results are the same bytes.
+
+    copy_to (CRC-only sets) also gathers the objects, in the pass that hashes them, through
+    efes_crc32_copy: each object's extents are written one behind the other, in the object's byte order,
+    starting at the device address copy_to + copy_offsets[i].  The default copy_offsets are those of
+    default_copy_offsets(objects); .copy_offsets holds the offsets in use and .copy_bytes the room they
+    need behind copy_to.  The destination must not overlap the source, the states or the sums.
     """
 
     _ordered = DeviceBatch._ordered
 
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
-                 crc32: bool = True, states: np.ndarray | None = None, walk=None):
+                 crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
+                 copy_offsets=None):
+        if copy_to is not None and sha1:
+            raise ValueError("DeviceObjects: copy_to= is CRC-only (efes_crc32_copy); build the set with sha1=False")
+        if copy_offsets is not None and copy_to is None:
+            raise ValueError("DeviceObjects: copy_offsets= needs copy_to=")
         import torch
 
         if not (sha1 or crc32):
@@ -292,6 +319,21 @@ class DeviceObjects:
         self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
         # allocated once and kept: one object set's launches run in stream order
         scratch_bytes = hash_chain_scratch(n) if sha1 else crc32_chain_scratch(n)
+        self.copy_to = copy_to
+        if copy_to is not None:
+            sizes = np.array([sum(int(m) for _, m in o) for o in objects], dtype=np.uint64)
+            if copy_offsets is None:
+                self.copy_offsets, self.copy_bytes = default_copy_offsets(objects)
+            else:
+                self.copy_offsets = np.asarray(copy_offsets, dtype=np.uint64)
+                assert self.copy_offsets.size == self.nobjects
+                self.copy_bytes = int((self.copy_offsets + sizes).max()) if self.nobjects else 0
+            # each extent behind the extents before it in its object
+            before = np.cumsum(ext[:, 1]) - ext[:, 1]
+            within = before - before[self.first[owner.astype(np.int64)]] if n else before
+            dst = np.uint64(copy_to) + self.copy_offsets[owner.astype(np.int64)] + within
+            self._dst = torch.from_numpy(dst.astype(np.uint64).view(np.uint8).copy()).to(device) if n else torch.zeros(8, dtype=torch.uint8, device=device)
+            scratch_bytes = crc32_copy_scratch(n)
         self._scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=device)
         torch.cuda.synchronize(device)
 
@@ -306,6 +348,10 @@ class DeviceObjects:
         if self.walk is not None:
             self._ordered(lambda stream: self.ctx.hash_chain_mode(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
                                                                   self._scratch.numel(), stream, self.walk))
+            return
+        if self.copy_to is not None:
+            self._ordered(lambda stream: self.ctx.crc32_copy(self.jobs.data_ptr(), self._dst.data_ptr(), self.n,
+                                                             self._scratch.data_ptr(), self._scratch.numel(), stream))
             return
         call = self.ctx.hash_chain if self.has_sha1 else self.ctx.crc32_chain
         self._ordered(lambda stream: call(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),

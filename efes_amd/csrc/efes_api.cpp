@@ -377,6 +377,19 @@ int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* 
   return hip_err(efes::launch_crc_chain(jobs, njobs, scratch, ctx->d_tabs, ctx->d_batch, ctx->cus, pick(ctx, stream)));
 }
 
+size_t efes_crc32_copy_scratch(uint32_t njobs) { return efes::crc_chain_scratch_bytes(njobs); }
+
+int efes_crc32_copy(efes_ctx* ctx, const efes_job* jobs, void* const* dst, uint32_t njobs, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (!ctx || (!jobs && njobs) || njobs > EFES_CRC_BATCH_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!dst) return EFES_ERR_ARG;  // nothing to copy to: efes_crc32_chain
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::crc_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_crc_copy(jobs, dst, njobs, scratch, ctx->d_tabs, ctx->d_batch, ctx->cus, pick(ctx, stream)));
+}
+
 size_t efes_hash_chain_scratch(uint32_t njobs) { return efes::hash_chain_scratch_bytes(njobs); }
 
 int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, void* scratch, size_t scratch_bytes,

@@ -1,5 +1,6 @@
 // efes_crc_batch.hip -- CRC-32/IEEE of MANY device buffers in one call, each spread over the whole GPU
-// (efes_crc32_batch, ABI 8), and of objects that lie in many extents (efes_crc32_chain, further down).
+// (efes_crc32_batch, ABI 8), of objects that lie in many extents (efes_crc32_chain, further down), and
+// the same with the bytes copied to a destination per job in the pass that hashes them (efes_crc32_copy).
 //
 // CRC-only jobs of efes_hash_submit run in the SHA-1-shaped kernels, one wavefront per job at best,
 // although CRC-32 is GF(2)-linear and needs no chain (efes_crc_span.hip has the identities).  Here
@@ -69,8 +70,29 @@
 //   chain_map_kernel      68 VGPRs, 43 SGPRs,    256 B LDS, no scratch, no spills, 7 waves/SIMD
 //   chain_carry_kernel    68 VGPRs, 39 SGPRs,    256 B LDS, no scratch, no spills, 7 waves/SIMD
 //   chain_finish_kernel   50 VGPRs, 20 SGPRs,      0 B LDS, no scratch, no spills, 8 waves/SIMD
+//
+// Copy with CRC (efes_crc32_copy): efes_crc32_chain with two of its five launches replaced by copying
+// instantiations of the same code; prep, carry and finish are reused, and so is the scratch layout.
+//   * batch_tile_kernel<true>: the tile pass holds every 16-byte piece of every job in registers, so it
+//     stores each piece it hashes to dst[job] + head + 16 piece, under the predicate that guards the
+//     piece's load (zero-padded pieces are never stored).  The source side is 16-byte aligned by
+//     construction (job_geo); the destination of a piece is not, so the store goes through a pointer
+//     of alignment 1: still one global_store_dwordx4, and a wave still writes 1 KiB contiguously.
+//     Plain stores; relative misalignment costs under 2 % (DESIGN.md §4 "Copy with CRC").
+//     dst[job] == NULL: no store.
+//     batch_tile_kernel<false> is the pass of the other two calls: its code differs from the
+//     untemplated kernel's in the order of two scalar moves.
+//   * copy_map_kernel: chain_map_kernel whose lane also lands the job's head and rest bytes, which it
+//     reads byte by byte anyway.  It skips what chain_map_kernel skips: a job with sha1 != NULL or
+//     crc32 == NULL, which has no tiles either, is not copied at all; a member that is invalid by its
+//     flags or its state pointer has its pieces copied (validity is known only after the scan) but not
+//     its head and rest.
+//   batch_tile_kernel<true>  107 VGPRs, 103 SGPRs, 82 432 B LDS, no scratch, no spills, 4 waves/SIMD
+//   copy_map_kernel           68 VGPRs,  43 SGPRs,    256 B LDS, no scratch, no spills, 7 waves/SIMD
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "efes_gf2.hpp"
 #include "efes_internal.hpp"
@@ -91,6 +113,7 @@ static_assert(kMaxBlocks <= kBatchLanes, "one lane per block sum");
 static_assert(kTile * kBatchTileOps == (1ull << 24), "tile_op covers 2^24 bytes (batch_flush)");
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef v4u v4u_u __attribute__((aligned(1)));  // a piece at its destination (efes_crc32_copy): any alignment
 
 // Scratch: bsum[kMaxBlocks] | loc[njobs] | acc[njobs] (main, last).
 struct Scratch {
@@ -213,6 +236,7 @@ struct TileDesc {
   uint32_t job;
   uint64_t i, nt, np;
   const uint8_t* bulk;
+  uint8_t* dst;  // the copying pass: where bulk's bytes land (dst[job] + head), nullptr for a job that is not copied
 };
 
 struct BatchArgs {
@@ -222,14 +246,24 @@ struct BatchArgs {
   const BatchTables* batch;
   uint32_t njobs, nblocks;
 };
+struct CopyArgs : BatchArgs {  // the copying tile pass (efes_crc32_copy)
+  void* const* dsts;           // the call's pointer array, parallel to jobs
+};
 
-__device__ __forceinline__ void desc_of_job(const efes_job* __restrict__ jobs, uint32_t j, TileDesc& D) {
+template <bool kCopy>
+__device__ __forceinline__ void desc_of_job(const efes_job* __restrict__ jobs, void* const* __restrict__ dsts, uint32_t j,
+                                            TileDesc& D) {
   const Geo g = job_geo(reinterpret_cast<const void*>(uni64(reinterpret_cast<uint64_t>(jobs[j].data))), uni64(jobs[j].length));
   D.job = j;
   D.i = 0;
   D.np = g.np;
   D.nt = tiles_of(g.np);
   D.bulk = g.bulk;
+  D.dst = nullptr;
+  if (kCopy) {
+    uint8_t* o = reinterpret_cast<uint8_t*>(uni64(reinterpret_cast<uint64_t>(dsts[j])));
+    if (o) D.dst = o + g.head;
+  }
 }
 
 // The lane's pieces of tile D: piece 256 wave + 64 k + lane, zero where the bulk has ended.
@@ -245,8 +279,21 @@ __device__ __forceinline__ void load_tile(const TileDesc& D, uint32_t first, v4u
   }
 }
 
-__global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs a) {
+// Piece p of a job's bulk to its destination: one plain 16-byte store at any alignment (a wave writes
+// 1 KiB contiguously).  Nontemporal stores were no faster (DESIGN.md §4 "Copy with CRC").
+__device__ __forceinline__ void store_piece(uint8_t* dst, uint64_t p, v4u v) {
+  *((__attribute__((address_space(1))) v4u_u*)dst + p) = v;
+}
+
+// The tile pass: batch_tile_kernel<false> is the pass of efes_crc32_batch and efes_crc32_chain.
+// batch_tile_kernel<true> (efes_crc32_copy) also stores every piece it hashes to its job's destination,
+// under the predicate that guards the piece's load, so the pieces load_tile zero-pads are never stored.
+// Without kCopy nothing of dsts or TileDesc::dst is left.
+template <bool kCopy>
+__global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const std::conditional_t<kCopy, CopyArgs, BatchArgs> a) {
   __shared__ __attribute__((aligned(16))) BatchLDS L;
+  void* const* __restrict__ dsts = nullptr;
+  if constexpr (kCopy) dsts = a.dsts;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const Scratch S = scratch_of(a.scratch, a.njobs);
   {  // tables into LDS: each slicing entry kCopies times, the two stride operators once
@@ -280,7 +327,7 @@ __global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs
     const uint32_t b = (uint32_t)__syncthreads_count(tid < a.nblocks && L.boff[tid] <= t0) - 1u;
     const uint64_t idx = (uint64_t)b * kPrefixBlock + tid;
     const uint32_t j = b * kPrefixBlock + (uint32_t)__syncthreads_count(excl(idx) <= t0) - 1u;
-    desc_of_job(a.jobs, uni32(j), D);
+    desc_of_job<kCopy>(a.jobs, dsts, uni32(j), D);
     D.i = t0 - uni64(excl(D.job));
   }
   // The job of tile t (> D's tile), which is not in D's job: the last job behind D.job that starts at
@@ -313,7 +360,7 @@ __global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs
       N.i = D.i + 1;
     } else {
       const uint32_t base = D.job + 1u;
-      desc_of_job(a.jobs, next_job(base, excl((uint64_t)base + lane), t0 + 1), N);
+      desc_of_job<kCopy>(a.jobs, dsts, next_job(base, excl((uint64_t)base + lane), t0 + 1), N);
     }
   }
   uint32_t acc = 0, parity = 0;
@@ -328,7 +375,7 @@ __global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs
     TileDesc spec = N;  // the job right behind N's, the usual successor
     if (have_next2 && !same2) {
       e2 = excl((uint64_t)base2 + lane);
-      desc_of_job(a.jobs, base2 < a.njobs ? base2 : a.njobs - 1u, spec);
+      desc_of_job<kCopy>(a.jobs, dsts, base2 < a.njobs ? base2 : a.njobs - 1u, spec);
     }
 
     // ---- hash tile D from cur
@@ -337,6 +384,7 @@ __global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
       if (p0 + 64u * k < D.np) {
+        if (kCopy && D.dst) store_piece(D.dst, p0 + 64u * k, cur[k]);
         const uint32_t raw = piece_raw(L, lb, sel, cur[k]);
         acc = shift_fold(k == 0 ? L.tile_shift : L.lane_shift, acc, raw);
         kv = k + 1;
@@ -380,7 +428,7 @@ __global__ __launch_bounds__(kBatchLanes) void batch_tile_kernel(const BatchArgs
       } else {
         const uint32_t j2 = next_job(base2, e2, t + 2);
         if (j2 == spec.job) N2 = spec;
-        else desc_of_job(a.jobs, j2, N2);
+        else desc_of_job<kCopy>(a.jobs, dsts, j2, N2);
       }
     }
     if (have_next) {
@@ -521,10 +569,12 @@ __device__ __forceinline__ bool follower_bad(const efes_job& jb, const efes_crc3
          (jb.flags & (EFES_JOB_INIT | EFES_JOB_SUM_ONLY)) != 0u || (prev_flags & EFES_JOB_SUM_ONLY) != 0u;
 }
 
-__global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
-                                                                void* scratch, const Tables* __restrict__ tabs,
-                                                                const BatchTables* __restrict__ batch) {
-  __shared__ uint4 wtot[kWaves];
+// The map pass.  kCopy (efes_crc32_copy): the lane also lands the job's head and rest bytes, which it
+// reads byte by byte anyway, at dsts[j] and behind the bulk's pieces there.
+template <bool kCopy>
+__device__ __forceinline__ void map_pass(const efes_job* __restrict__ jobs, uint32_t njobs, void* scratch,
+                                         const Tables* __restrict__ tabs, const BatchTables* __restrict__ batch,
+                                         void* const* __restrict__ dsts, uint4* wtot) {
   const uint32_t j = blockIdx.x * kPrefixBlock + threadIdx.x;
   const ChainScratch C = chain_scratch_of(scratch, njobs);
   Aff e = aff_identity();  // the lanes past the array
@@ -539,11 +589,16 @@ __global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* 
       const uint32_t* t0 = tabs->slice8[0];
       const uint8_t* d = static_cast<const uint8_t*>(jb.data);
       const Geo g = job_geo(jb.data, jb.length);
+      uint8_t* o = kCopy ? static_cast<uint8_t*>(dsts[j]) : nullptr;
       // The register after the head bytes: from the in-state for a head (crc32.go:123), whose map then
       // forgets what came before (m = 0), from zero for a follower.
       uint32_t r = 0;
       if (!chained) r = (jb.flags & EFES_JOB_INIT) ? 0xFFFFFFFFu : ~jb.crc32->crc;
-      for (uint32_t i = 0; i < g.head; ++i) r = t0[(r ^ d[i]) & 0xffu] ^ (r >> 8);  // crc32.go:125
+      for (uint32_t i = 0; i < g.head; ++i) {
+        const uint8_t c = d[i];
+        if (kCopy && o) o[i] = c;
+        r = t0[(r ^ c) & 0xffu] ^ (r >> 8);  // crc32.go:125
+      }
       const uint32_t behind_head = xpow8n(jb.length - g.head, batch->x2n);
       if (r) r = gf2_mulmod(behind_head, r);
       uint32_t t = 0;  // the bulk's raw CRC from the two accumulators, as batch_finish_kernel combines them
@@ -555,7 +610,12 @@ __global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* 
       }
       // one table step is x^8: going on byte-wise from t gives Z^rest(bulk) ^ raw(rest)
       const uint8_t* rest = g.bulk + 16 * g.np;
-      for (uint32_t i = 0; i < g.rest; ++i) t = t0[(t ^ rest[i]) & 0xffu] ^ (t >> 8);
+      uint8_t* orest = o ? o + g.head + 16 * g.np : nullptr;
+      for (uint32_t i = 0; i < g.rest; ++i) {
+        const uint8_t c = rest[i];
+        if (kCopy && o) orest[i] = c;
+        t = t0[(t ^ c) & 0xffu] ^ (t >> 8);
+      }
       e.b = r ^ t;
       if (chained) {  // m = x^(8 length): the head's zero bytes applied to x^(8 (length - head))
         e.m = behind_head;
@@ -566,6 +626,21 @@ __global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* 
   e = block_scan_aff(e, wtot);
   if (j < njobs) C.elem[j] = aff_pack(e);
   if (threadIdx.x == kPrefixBlock - 1u) C.btot[blockIdx.x] = aff_pack(e);
+}
+
+__global__ __launch_bounds__(kBatchLanes) void chain_map_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                void* scratch, const Tables* __restrict__ tabs,
+                                                                const BatchTables* __restrict__ batch) {
+  __shared__ uint4 wtot[kWaves];
+  map_pass<false>(jobs, njobs, scratch, tabs, batch, nullptr, wtot);
+}
+
+__global__ __launch_bounds__(kBatchLanes) void copy_map_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                               void* scratch, const Tables* __restrict__ tabs,
+                                                               const BatchTables* __restrict__ batch,
+                                                               void* const* __restrict__ dsts) {
+  __shared__ uint4 wtot[kWaves];
+  map_pass<true>(jobs, njobs, scratch, tabs, batch, dsts, wtot);
 }
 
 // btot[k] becomes the map of the blocks 0..k together.  One workgroup of at least nblocks lanes.
@@ -629,15 +704,16 @@ size_t crc_batch_scratch_bytes(uint32_t njobs) {
   return batch_scratch_size(njobs);
 }
 
-// The two launches every path starts with: tiles per job, then the tiles.
+// The two launches every path starts with: tiles per job, then the tiles (dsts: the copying tile pass).
 static hipError_t launch_prep_and_tiles(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
-                                        const BatchTables* batch, int cus, hipStream_t s) {
+                                        const BatchTables* batch, int cus, hipStream_t s, void* const* dsts = nullptr) {
   const uint32_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
   clear_last_error();
   hipLaunchKernelGGL(batch_prep_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  BatchArgs a{};
+  CopyArgs a{};
+  a.dsts = dsts;
   a.jobs = jobs;
   a.scratch = scratch;
   a.tabs = tabs;
@@ -645,7 +721,9 @@ static hipError_t launch_prep_and_tiles(const efes_job* jobs, uint32_t njobs, vo
   a.njobs = njobs;
   a.nblocks = nblocks;
   clear_last_error();
-  hipLaunchKernelGGL(batch_tile_kernel, dim3((uint32_t)(cus > 0 ? cus : 256)), dim3(kBatchLanes), 0, s, a);
+  const dim3 grid((uint32_t)(cus > 0 ? cus : 256));
+  if (dsts) hipLaunchKernelGGL(batch_tile_kernel<true>, grid, dim3(kBatchLanes), 0, s, a);
+  else hipLaunchKernelGGL(batch_tile_kernel<false>, grid, dim3(kBatchLanes), 0, s, static_cast<const BatchArgs&>(a));
   return hipGetLastError();
 }
 
@@ -664,13 +742,15 @@ size_t crc_chain_scratch_bytes(uint32_t njobs) {
   return batch_scratch_size(njobs) + sizeof(uint4) * ((size_t)njobs + nblocks);
 }
 
-hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
-                            const BatchTables* batch, int cus, hipStream_t s) {
+// efes_crc32_chain, and with dsts efes_crc32_copy: the copying tile and map passes in place of the plain ones.
+static hipError_t launch_chain(const efes_job* jobs, void* const* dsts, uint32_t njobs, void* scratch, const Tables* tabs,
+                               const BatchTables* batch, int cus, hipStream_t s) {
   const uint32_t nblocks = (njobs + kPrefixBlock - 1) / kPrefixBlock;
-  hipError_t e = launch_prep_and_tiles(jobs, njobs, scratch, tabs, batch, cus, s);
+  hipError_t e = launch_prep_and_tiles(jobs, njobs, scratch, tabs, batch, cus, s, dsts);
   if (e != hipSuccess) return e;
   clear_last_error();
-  hipLaunchKernelGGL(chain_map_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch, tabs, batch);
+  if (dsts) hipLaunchKernelGGL(copy_map_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch, tabs, batch, dsts);
+  else hipLaunchKernelGGL(chain_map_kernel, dim3(nblocks), dim3(kBatchLanes), 0, s, jobs, njobs, scratch, tabs, batch);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (nblocks > 1) {  // one block of jobs has no carry to take
@@ -682,6 +762,16 @@ hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch,
   clear_last_error();
   hipLaunchKernelGGL(chain_finish_kernel, dim3((njobs + 255u) / 256u), dim3(256), 0, s, jobs, njobs, scratch);
   return hipGetLastError();
+}
+
+hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
+                            const BatchTables* batch, int cus, hipStream_t s) {
+  return launch_chain(jobs, nullptr, njobs, scratch, tabs, batch, cus, s);
+}
+
+hipError_t launch_crc_copy(const efes_job* jobs, void* const* dsts, uint32_t njobs, void* scratch, const Tables* tabs,
+                           const BatchTables* batch, int cus, hipStream_t s) {
+  return launch_chain(jobs, dsts, njobs, scratch, tabs, batch, cus, s);
 }
 
 }  // namespace efes

@@ -156,6 +156,10 @@ hipError_t launch_crc_batch(const efes_job* jobs, uint32_t njobs, void* scratch,
 size_t crc_chain_scratch_bytes(uint32_t njobs);
 hipError_t launch_crc_chain(const efes_job* jobs, uint32_t njobs, void* scratch, const Tables* tabs,
                             const BatchTables* batch, int cus, hipStream_t s);
+// Copy with CRC (efes_crc32_copy): launch_crc_chain over the same scratch, with a tile pass that also
+// stores every piece it hashes at dsts[job] and a map pass that lands the head and rest bytes.
+hipError_t launch_crc_copy(const efes_job* jobs, void* const* dsts, uint32_t njobs, void* scratch, const Tables* tabs,
+                           const BatchTables* batch, int cus, hipStream_t s);
 // Chained SHA-1 + CRC jobs (efes_hash_chain, efes_kernels.hip): two prep launches list the chains'
 // heads in the scratch (16 bytes, 4 per block of 1024 jobs at the maximum count, 8 per job), then a
 // persistent launch in which each wavefront draws whole chains by a ticket.

@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -53,6 +53,12 @@ def crc32_chain_scratch(n: int) -> int:
     """efes_crc32_chain_scratch: device bytes efes_crc32_chain needs for n jobs (0 for n == 0 or more
     than EFES_CRC_BATCH_MAX_JOBS; never less than crc32_batch_scratch(n))."""
     return int(lib().efes_crc32_chain_scratch(n))
+
+
+def crc32_copy_scratch(n: int) -> int:
+    """efes_crc32_copy_scratch: device bytes efes_crc32_copy needs for n jobs (0 for n == 0 or more than
+    EFES_CRC_BATCH_MAX_JOBS; never less than crc32_chain_scratch(n))."""
+    return int(lib().efes_crc32_copy_scratch(n))
 
 
 def hash_chain_scratch(n: int) -> int:
@@ -117,6 +123,13 @@ class Context:
         Write into the state of the job before it, so one object may lie in many extents; scratch:
         crc32_chain_scratch(njobs) device bytes, otherwise as for crc32_batch."""
         check(lib().efes_crc32_chain(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_chain")
+
+    def crc32_copy(self, jobs_ptr: int, dst_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
+                   stream: int | None = None) -> None:
+        """efes_crc32_copy: crc32_chain() that also copies each job's bytes, in the same pass over them, to
+        the device pointer dst[j] of the device array at dst_ptr (any alignment; 0: hashed, not copied);
+        scratch: crc32_copy_scratch(njobs) device bytes, otherwise as for crc32_chain."""
+        check(lib().efes_crc32_copy(self.handle, jobs_ptr, dst_ptr, njobs, scratch_ptr, scratch_bytes, stream), "efes_crc32_copy")
 
     def hash_chain(self, jobs_ptr: int, njobs: int, scratch_ptr: int, scratch_bytes: int,
                    stream: int | None = None) -> None:

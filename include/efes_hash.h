@@ -465,6 +465,57 @@ size_t efes_crc32_chain_scratch(uint32_t njobs);
 int efes_crc32_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
                      size_t scratch_bytes, void* stream);
 
+/* Copy with CRC: move device extents and CRC them in ONE pass over their bytes -- io.MultiWriter(f, CRC32)
+ * with a device destination as the first writer (filereceiver.go:208-209): gather an object's extents
+ * into one contiguous buffer before a write-out, compact a pool, move a drained object.
+ * efes_crc32_copy is efes_crc32_chain plus a copy of each job's bytes.  Everything of the chain call
+ * carries over: the same device job array, EFES_JOB_CHAIN / INIT / FINALIZE / SUM_ONLY, every validity
+ * rule, status, state store and per-member sum, lengths read on the device, no host read-back,
+ * allocation or wait, asynchronous on `stream`, njobs <= EFES_CRC_BATCH_MAX_JOBS, njobs == 0 returns
+ * EFES_OK and launches nothing, the same scratch rules with efes_crc32_copy_scratch(njobs) bytes (>=
+ * efes_crc32_chain_scratch(njobs), 0 where that is 0).  On any job array everything efes_crc32_chain
+ * writes is written byte for byte the same.  The copy:
+ *   - dst_device is a device array of njobs device pointers, parallel to jobs_device.  dst[j] may have
+ *     any alignment, independent of the alignment of jobs[j].data; dst[j] == NULL: job j is hashed and
+ *     not copied.  A NULL dst_device with njobs > 0 returns EFES_ERR_ARG: use efes_crc32_chain;
+ *   - a valid job's `length` bytes are written to [dst[j], dst[j] + length), exactly.  No byte outside
+ *     that range is written for any job, valid or not; a zero-length job writes nothing;
+ *   - a job with sha1 != NULL or crc32 == NULL is not read, and nothing is copied for it;
+ *   - a chain member that is invalid for any other reason (it names another state, carries
+ *     EFES_JOB_INIT or EFES_JOB_SUM_ONLY, follows an EFES_JOB_SUM_ONLY job or an invalid member, or is a
+ *     flagged job 0) may or may not have had its bytes written: after the call every byte of its
+ *     destination range holds either its old value or the source byte, unspecified which -- chain
+ *     validity is known only after the scan, which runs behind the pass that moves the bytes.  Its
+ *     status and everything else are as in the chain call;
+ *   - destination ranges must not overlap each other, nor any job's source range, the states, sums,
+ *     statuses, the job array, the pointer array or the scratch.  Like "jobs must not share a state"
+ *     this is the caller's contract and is not checked;
+ *   - the destination bytes are visible to later work in stream order, like the states.
+ * The tile pass that hashes a job's 16-byte pieces stores each piece from the registers it was loaded
+ * into (one plain 16-byte store per piece, at whatever alignment the destination has); the scan's map
+ * pass lands the up to 15 bytes before and behind the pieces.  EFES_ABI_VERSION stays 8: the call is an addition, and a binding detects
+ * it by the symbol.
+ * Which path when, continued (measured on a 4 GiB source and a 4 GiB destination per shape,
+ * profiles/crc_copy/bench.json; DESIGN.md §4 "Copy with CRC" has the table):
+ *   - extents that have to be moved AND checked (gather before a write-out, pool compaction, a drained
+ *     object's move): efes_crc32_copy.  The yardstick is the best single-launch copy (one memcpy for
+ *     16 x 256 MiB, one strided copy in 16-byte elements for the transposing gathers) followed by
+ *     efes_crc32_chain over the source.  The call takes about 0.7 of that time at 16 x 256 MiB and at
+ *     64 objects x 64 extents x 1 MiB and about 0.6 at 1024 objects x 64 extents x 64 KiB, its median
+ *     below the two-call path's minimum on all three: the second read of the bytes is gone, as the
+ *     traffic says (two thirds).  It moves 4.5 to 5.1 TB/s (read + written) and takes at most 1.25x the
+ *     time of the copy ALONE: the CRC rides along on a move that has to happen anyway;
+ *   - relative misalignment (destination + 1 byte or + 8 bytes against a 16-byte aligned source) costs
+ *     the call under 2 %, so no layout needs padding for it.  A strided copy loses its wide elements
+ *     there (single bytes at + 1: 3.3x its aligned time), which makes the call the faster MOVE for such
+ *     layouts, CRC or not;
+ *   - extents that are only checked, or that are moved by something that cannot hash (a DMA engine,
+ *     another GPU's copy): efes_crc32_chain, which reads the same bytes at about 5.6 TB/s and writes
+ *     nothing. */
+size_t efes_crc32_copy_scratch(uint32_t njobs);
+int efes_crc32_copy(efes_ctx* ctx, const efes_job* jobs_device, void* const* dst_device, uint32_t njobs,
+                    void* scratch_device, size_t scratch_bytes, void* stream);
+
 /* Chained SHA-1 + CRC-32 jobs: efes_hash_submit for objects that lie in MANY device extents.  The same
  * device job array as efes_hash_submit, fused, SHA-1-only or CRC-only jobs, lengths and flags read on
  * the device, no host read-back, allocation or wait, asynchronous on `stream` (NULL = the context
