@@ -101,6 +101,10 @@ JOB_DTYPE = np.dtype([("data", "<u8"), ("length", "<u8"), ("sha1", "<u8"), ("crc
 SHA1_STATE_DTYPE = np.dtype([("h", "<u4", (5,)), ("x", "u1", (64,)), ("_pad", "<u4"), ("nx", "<i8"),
                              ("len", "<u8")])
 assert JOB_DTYPE.itemsize == 56 and SHA1_STATE_DTYPE.itemsize == 104
+# efes_checkpoint: the resumable state after one member of a chain (efes_hash_chain_checkpoints)
+CHECKPOINT_DTYPE = np.dtype([("sha1", SHA1_STATE_DTYPE), ("crc", "<u4"), ("_pad", "<u4")])
+CHECKPOINT_TEXT_BYTES = 208  # EFES_CHECKPOINT_TEXT_BYTES: 200 characters of the SHA-1 state, 8 of the CRC
+assert CHECKPOINT_DTYPE.itemsize == 112
 
 # Every symbol declared in include/efes_hash.h: (restype, argtypes)
 _P, _S, _VP, _I, _U32, _U64 = ctypes.POINTER, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64
@@ -182,6 +186,8 @@ SIGNATURES = {
     "efes_hash_chain": (_I, [_VP, _VP, _U32, _VP, _S, _VP]),
     "efes_hash_chain_mode": (_I, [_VP, _VP, _U32, _VP, _S, _VP, _I]),
     "efes_hash_chain_auto_mode": (_I, [_VP, _U32]),
+    "efes_hash_chain_checkpoints": (_I, [_VP, _VP, _U32, _VP, _VP, _S, _VP, _I]),
+    "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),
     "efes_crc32_state_marshal_text": (None, [_P(Crc32State), _VP]),

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
+from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
 from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_scratch
 
@@ -253,6 +253,12 @@ class DeviceObjects:
     starting at the device address copy_to + copy_offsets[i].  The default copy_offsets are those of
     default_copy_offsets(objects); .copy_offsets holds the offsets in use and .copy_bytes the room they
     need behind copy_to.  The destination must not overlap the source, the states or the sums.
+
+    checkpoints=True (sha1=True only; a CRC-only set's running CRCs already are its checkpoints) also
+    keeps one 112-byte record per extent, contiguous in extent order, and always submits through
+    efes_hash_chain_checkpoints -- at the mode `walk` gives ("auto" as above), EFES_MODE_DEEP without one.
+    checkpoints_host() is the records (the resumable SHA-1 state and the CRC after each extent),
+    checkpoint_texts() their `.info` texts, marshalled on the device.
     """
 
     _ordered = DeviceBatch._ordered
@@ -260,7 +266,9 @@ class DeviceObjects:
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                  crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                 copy_offsets=None):
+                 copy_offsets=None, checkpoints: bool = False):
+        if checkpoints and not sha1:
+            raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
         if copy_to is not None and sha1:
             raise ValueError("DeviceObjects: copy_to= is CRC-only (efes_crc32_copy); build the set with sha1=False")
         if copy_offsets is not None and copy_to is None:
@@ -317,6 +325,13 @@ class DeviceObjects:
         self.walk = hash_chain_auto_mode(int((counts > 0).sum()), self.ctx) if walk == "auto" else walk
         self.jobs_host = jobs
         self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
+        self.has_checkpoints = bool(checkpoints)
+        if checkpoints:  # one record per extent, ckpt[j] = base + 112 j
+            if self.walk is None:
+                self.walk = MODE_DEEP
+            self.ckpt = torch.zeros(max(n, 1) * CHECKPOINT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+            at = np.uint64(self.ckpt.data_ptr()) + idx * np.uint64(CHECKPOINT_DTYPE.itemsize)
+            self._ckpt_ptrs = torch.from_numpy(at.astype(np.uint64).view(np.uint8).copy()).to(device) if n else torch.zeros(8, dtype=torch.uint8, device=device)
         # allocated once and kept: one object set's launches run in stream order
         scratch_bytes = hash_chain_scratch(n) if sha1 else crc32_chain_scratch(n)
         self.copy_to = copy_to
@@ -345,6 +360,11 @@ class DeviceObjects:
                 self.states.copy_(self._init_states_dev)
 
     def submit(self) -> None:
+        if self.has_checkpoints:
+            self._ordered(lambda stream: self.ctx.hash_chain_checkpoints(self.jobs.data_ptr(), self.n, self._ckpt_ptrs.data_ptr(),
+                                                                         self._scratch.data_ptr(), self._scratch.numel(),
+                                                                         stream, self.walk))
+            return
         if self.walk is not None:
             self._ordered(lambda stream: self.ctx.hash_chain_mode(self.jobs.data_ptr(), self.n, self._scratch.data_ptr(),
                                                                   self._scratch.numel(), stream, self.walk))
@@ -397,6 +417,25 @@ class DeviceObjects:
         """Per object: the SHA-1 state after its last extent (h, x with its stale bytes, nx, len)."""
         self._need_sha1("states_host")
         return self.states.cpu().numpy().view(SHA1_STATE_DTYPE)[: self.nobjects]
+
+    def _need_checkpoints(self, what: str) -> None:
+        if not self.has_checkpoints:
+            raise ValueError(f"{what}: build the set with sha1=True, checkpoints=True")
+
+    def checkpoints_host(self) -> np.ndarray:
+        """Per extent: the record after that extent's Write (CHECKPOINT_DTYPE: the SHA-1 state with its
+        stale bytes, the CRC)."""
+        self._need_checkpoints("checkpoints_host")
+        return self.ckpt.cpu().numpy().view(CHECKPOINT_DTYPE)[: self.n]
+
+    def checkpoint_texts(self) -> list:
+        """Per extent: (sha1_text, crc32_text) as bytes, 200 and 8 characters, what `.info` holds after
+        that extent's PATCH; marshalled on the device by efes_checkpoints_marshal_text."""
+        self._need_checkpoints("checkpoint_texts")
+        text = self.torch.empty(max(self.n, 1) * CHECKPOINT_TEXT_BYTES, dtype=self.torch.uint8, device=self.device)
+        self._ordered(lambda stream: self.ctx.checkpoints_marshal_text(self.ckpt.data_ptr(), self.n, text.data_ptr(), stream))
+        rows = text.cpu().numpy()[: self.n * CHECKPOINT_TEXT_BYTES].reshape(self.n, CHECKPOINT_TEXT_BYTES)
+        return [(bytes(r[:200]), bytes(r[200:])) for r in rows]
 
 
 class PinnedHostBuffer:

@@ -427,6 +427,33 @@ int efes_hash_chain_mode(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, vo
       efes::launch_hash_chain_group(jobs, njobs, lanes, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
 }
 
+static_assert(sizeof(efes_checkpoint) == 112 && alignof(efes_checkpoint) == 8 &&
+                  offsetof(efes_checkpoint, crc32) == sizeof(efes_sha1_state),
+              "efes_checkpoint: the SHA-1 state, the CRC, 4 bytes of padding");
+static_assert(EFES_CHECKPOINT_TEXT_BYTES == 200 + 8, "sha1_efes.go:25-38 then crc32_efes.go:18-24");
+
+int efes_hash_chain_checkpoints(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, efes_checkpoint* const* ckpt,
+                                void* scratch, size_t scratch_bytes, void* stream, int mode) {
+  const int lanes = efes::group_of_mode(mode);
+  if (mode != EFES_MODE_DEEP && !lanes) return EFES_ERR_ARG;  // AUTO too, as efes_hash_chain_mode
+  if (!ctx || (!jobs && njobs) || njobs > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!ckpt) return EFES_ERR_ARG;  // no record asked for: efes_hash_chain_mode
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::hash_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(
+      efes::launch_hash_chain_ckpt(jobs, njobs, lanes, ckpt, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
+}
+
+int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, uint32_t n, char* text, void* stream) {
+  if (!ctx || n > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (n == 0) return EFES_OK;
+  if (!ckpt || !text) return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_checkpoint_text(ckpt, n, text, pick(ctx, stream)));
+}
+
 int efes_crc32_tables(uint32_t* out, size_t nwords) {
   const size_t need = sizeof(Tables) / 4, with_pos = need + sizeof(efes::PosTables) / 4;
   if (!out || nwords < need) return EFES_ERR_ARG;

@@ -170,6 +170,12 @@ hipError_t launch_hash_chain(const efes_job* jobs, uint32_t njobs, void* scratch
 // in which each wavefront holds 64/G chains at once, G in {4, 8, 16, 32}, and advances them together.
 hipError_t launch_hash_chain_group(const efes_job* jobs, uint32_t njobs, int G, void* scratch, const Tables* tabs,
                                    int cus, hipStream_t s);
+// Either walk with checkpoints (efes_hash_chain_checkpoints): G == 0 is the wave walk, else the grouped
+// walk; kernels of their own that also store ckpt[j] after every member that is due a record.
+hipError_t launch_hash_chain_ckpt(const efes_job* jobs, uint32_t njobs, int G, efes_checkpoint* const* ckpt,
+                                  void* scratch, const Tables* tabs, int cus, hipStream_t s);
+// The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
+hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

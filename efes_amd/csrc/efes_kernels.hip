@@ -651,7 +651,7 @@ __device__ __forceinline__ uint32_t crc_block_pos(const uint32_t (&pos)[64][256]
 
 // kSha / kCrc are wave-uniform (any joining job needs the hash): with both, the CRC lookups and
 // the schedule expansion share one basic block, so the lookups' latency hides behind VALU work.
-// kUser: the kernel that calls it (0 group_kernel, 1 hash_chain_group_kernel), so that each has an
+// kUser: the kernel that calls it (0 group_kernel, 1 hash_chain_group_kernel, 2 hash_chain_group_ckpt_kernel), so that each has an
 // instantiation of its own, with one call site, and compiles as if the other did not exist.
 template <int G, bool kAligned16, bool kSha, bool kCrc, int kUser = 0>
 __device__ void group_bulk(const Tables& T, const PosTables& P, int lane, DeepMsg* msgs, uint64_t S) {
@@ -1764,8 +1764,37 @@ struct ChainLDS {
 };
 static_assert(sizeof(ChainLDS) > kCuLds / 2 && sizeof(ChainLDS) <= 96 * 1024, "one chain workgroup per CU");
 
-__global__ __launch_bounds__(64 * kDeepWaves) void hash_chain_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
-                                                                     const Tables* __restrict__ tabs, void* scratch) {
+// The drain and agent-scope fence between a deep_rest and what loads the state it stored.
+__device__ __forceinline__ void chain_fence() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// One member's checkpoint (efes_hash_chain_checkpoints), behind a chain_fence() after the member's
+// deep_rest<true>: the state deep_rest stored is read back, one 32-bit word per lane (the addresses differ
+// by lane, so these are vector loads, which the fence covers), and all 28 words of the record are
+// written -- zero for the _pad words and for the hash the chain does not keep.
+__device__ __forceinline__ void chain_checkpoint(int lane, const DeepJob& J, efes_checkpoint* ck) {
+  constexpr int kStateWords = (int)(sizeof(efes_sha1_state) / 4);
+  constexpr int kPadWord = (int)(offsetof(efes_sha1_state, _pad) / 4);
+  constexpr int kCrcWord = (int)(offsetof(efes_checkpoint, crc32) / 4);
+  constexpr int kWords = (int)(sizeof(efes_checkpoint) / 4);
+  static_assert(kCrcWord == kStateWords && kWords == kCrcWord + 2 && kWords <= 64, "one lane per word of the record");
+  uint32_t* src = nullptr;
+  if (lane < kStateWords && lane != kPadWord && J.st) src = reinterpret_cast<uint32_t*>(J.st) + lane;
+  if (lane == kCrcWord && J.cs) src = &J.cs->crc;
+  uint32_t v = 0u;
+  if (src) v = *src;
+  if (lane < kWords) reinterpret_cast<uint32_t*>(ck)[lane] = v;
+}
+
+// The wave walk.  kCkpt: also leave a checkpoint after every member that is due one (ckpt[j] != NULL, the
+// Write took effect, no EFES_JOB_SUM_ONLY); without it ckpt is not read.
+template <bool kCkpt>
+__device__ __forceinline__ void hash_chain_walk(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                const Tables* __restrict__ tabs, void* scratch,
+                                                efes_checkpoint* const* __restrict__ ckpt) {
   __shared__ __attribute__((aligned(16))) ChainLDS L;
   {
     const uint4* src = reinterpret_cast<const uint4*>(tabs);
@@ -1799,19 +1828,28 @@ __global__ __launch_bounds__(64 * kDeepWaves) void hash_chain_kernel(const efes_
         if (lane == 0 && J.status) *J.status = EFES_ERR_ARG;
         continue;
       }
-      if (wrote) {  // the member before stored the state this one loads
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      if (wrote) chain_fence();  // the member before stored the state this one loads
       const DeepMsg M = deep_head(L.tab, lane, J, L.xs[wave]);
       if (M.live) deep_rest<true>(L.tab, lane, J, L.xs[wave], L.fin[wave], M);
       wrote = true;
+      if (kCkpt && M.live && (J.flags & EFES_JOB_SUM_ONLY) == 0u) {
+        efes_checkpoint* ck = reinterpret_cast<efes_checkpoint*>(uniform64(reinterpret_cast<uint64_t>(ckpt[j])));
+        if (ck) {
+          chain_fence();
+          chain_checkpoint(lane, J, ck);
+          wrote = false;  // the fence has passed: the next member's stands here
+        }
+      }
       prev_st = J.st;
       prev_cs = J.cs;
       prev_flags = J.flags;
     }
   }
+}
+
+__global__ __launch_bounds__(64 * kDeepWaves) void hash_chain_kernel(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                                     const Tables* __restrict__ tabs, void* scratch) {
+  hash_chain_walk<false>(jobs, njobs, tabs, scratch, nullptr);
 }
 
 size_t hash_chain_scratch_bytes(uint32_t njobs) {
@@ -1894,11 +1932,10 @@ struct ChainGroupLDS {
 };
 static_assert(sizeof(ChainGroupLDS) > kCuLds / 2 && sizeof(ChainGroupLDS) <= kCuLds, "one workgroup per CU");
 
-template <int G>
-__global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(const efes_job* __restrict__ jobs,
-                                                                              uint32_t njobs,
-                                                                              const Tables* __restrict__ tabs,
-                                                                              void* scratch) {
+template <int G, bool kCkpt>
+__device__ __forceinline__ void hash_chain_group_walk(const efes_job* __restrict__ jobs, uint32_t njobs,
+                                                      const Tables* __restrict__ tabs, void* scratch,
+                                                      efes_checkpoint* const* __restrict__ ckpt) {
   constexpr int kSlots = 64 / G;
   static_assert(kSlots <= kGroupMaxJobs, "LDS holds kGroupMaxJobs slots per wave");
   __shared__ __attribute__((aligned(16))) ChainGroupLDS L;
@@ -1948,8 +1985,18 @@ __global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(co
       for (;;) {
         if (M.live) {
           if (m != lone && M.nbulk - M.done >= (uint64_t)G) break;  // joinable
-          deep_rest<true>(L.d.tab, lane, load_job(jobs, C.cur, lane), L.d.xs[wave][m], L.d.fin[wave], M);
+          const DeepJob Jr = load_job(jobs, C.cur, lane);
+          deep_rest<true>(L.d.tab, lane, Jr, L.d.xs[wave][m], L.d.fin[wave], M);
           wrote = true;
+          if (kCkpt && (Jr.flags & EFES_JOB_SUM_ONLY) == 0u) {
+            efes_checkpoint* ck =
+                reinterpret_cast<efes_checkpoint*>(uniform64(reinterpret_cast<uint64_t>(ckpt[C.cur])));
+            if (ck) {
+              chain_fence();
+              chain_checkpoint(lane, Jr, ck);
+              wrote = false;
+            }
+          }
           M = DeepMsg{};
           ++C.cur;
         }
@@ -1988,9 +2035,7 @@ __global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(co
           continue;
         }
         if (wrote) {  // a member before stored the state this one may load
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          chain_fence();
           wrote = false;
         }
         M = deep_head(L.d.tab, lane, J, L.d.xs[wave][m]);
@@ -2029,9 +2074,18 @@ __global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(co
     if (joiners == 1) continue;  // step 1 runs slot `lone` to its member's end on the one-job path
     lone = -1;
     wave_lds_sync();
-    if (all16) group_bulk_any<G, true, 1>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
-    else group_bulk_any<G, false, 1>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
+    constexpr int kUser = kCkpt ? 2 : 1;  // an instantiation of group_bulk for each kernel (see Resources above)
+    if (all16) group_bulk_any<G, true, kUser>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
+    else group_bulk_any<G, false, kUser>(L.d.tab, L.d.pos, lane, msgs, St, any_sha, any_crc);
   }
+}
+
+template <int G>
+__global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_kernel(const efes_job* __restrict__ jobs,
+                                                                              uint32_t njobs,
+                                                                              const Tables* __restrict__ tabs,
+                                                                              void* scratch) {
+  hash_chain_group_walk<G, false>(jobs, njobs, tabs, scratch, nullptr);
 }
 
 template <int G>
@@ -2064,6 +2118,125 @@ hipError_t launch_hash_chain_group(const efes_job* jobs, uint32_t njobs, int G, 
     case 16: return launch_hash_chain_group_shape<16>(jobs, njobs, scratch, tabs, cus, s);
     default: return launch_hash_chain_group_shape<32>(jobs, njobs, scratch, tabs, cus, s);
   }
+}
+
+// ------------------------------------------------------------------ checkpoints (efes_hash_chain_checkpoints)
+// The resumable state after every member the caller asks for: the same prep launches, scratch, ticket and
+// heads[] list, then the wave walk or the grouped walk instantiated with kCkpt -- kernels of their own, so
+// hash_chain_kernel and hash_chain_group_kernel<*> stay the code they were.  Where a member ends in
+// deep_rest<true> (the wave walk's loop; step 1 of the grouped walk) and is due a record, the wave passes
+// the walks' drain and agent-scope fence at once instead of before the next deep_head, reads the stored
+// state back (chain_checkpoint: one word per lane, vector loads through the non-const state pointers) and
+// stores the 28 words of the record.  deep_rest itself is untouched: it is shared with the job kernels,
+// and the record needs nothing it does not already store.  The fence is the one the next member of this
+// wave would have passed anyway, so a checkpoint costs one load and one store round trip per member and
+// one more fence per chain (after its last member).  A member that is invalid, whose Write panics in Go
+// (deep_head's live == 0) or that carries EFES_JOB_SUM_ONLY never reaches the store; ckpt[] is read only
+// for members that do.  No wave waits for another; every loop bound comes from memory an earlier launch
+// wrote, or from the ticket; no LDS-DMA; the only inline assembly is the walks' wait.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   hash_chain_ckpt_kernel            144 VGPRs, 106 SGPRs,  87 040 B LDS, no scratch, no VGPR spills, 14 SGPRs kept in VGPR lanes
+//   hash_chain_group_ckpt_kernel<4>   215 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 59 SGPRs kept in VGPR lanes
+//   hash_chain_group_ckpt_kernel<8>   217 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 59 SGPRs kept in VGPR lanes
+//   hash_chain_group_ckpt_kernel<16>  217 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 65 SGPRs kept in VGPR lanes
+//   hash_chain_group_ckpt_kernel<32>  217 VGPRs, 106 SGPRs, 114 432 B LDS, no scratch, no VGPR spills, 61 SGPRs kept in VGPR lanes
+//   the five walks each 1 wave/SIMD (one workgroup per CU, by LDS), no AGPRs.
+//   checkpoint_text_kernel              8 VGPRs,  18 SGPRs,       0 B LDS, no scratch, no spills, 8 waves/SIMD
+// Every other kernel of this file compiles to the same registers, LDS, scratch and occupancy with and
+// without this section (group_bulk's kUser = 2 keeps the grouped walks' bulk step apart).
+__global__ __launch_bounds__(64 * kDeepWaves) void hash_chain_ckpt_kernel(const efes_job* __restrict__ jobs,
+                                                                          uint32_t njobs,
+                                                                          const Tables* __restrict__ tabs,
+                                                                          void* scratch,
+                                                                          efes_checkpoint* const* __restrict__ ckpt) {
+  hash_chain_walk<true>(jobs, njobs, tabs, scratch, ckpt);
+}
+
+template <int G>
+__global__ __launch_bounds__(64 * kDeepWaves, 1) void hash_chain_group_ckpt_kernel(
+    const efes_job* __restrict__ jobs, uint32_t njobs, const Tables* __restrict__ tabs, void* scratch,
+    efes_checkpoint* const* __restrict__ ckpt) {
+  hash_chain_group_walk<G, true>(jobs, njobs, tabs, scratch, ckpt);
+}
+
+// The persistent grid of a walk: the workgroups that njobs chains would fill, or what is resident.
+template <typename Kernel>
+static uint32_t chain_ckpt_grid(Kernel kernel, uint32_t njobs, uint64_t per_block, int cus) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * kDeepWaves, 0) != hipSuccess || per_cu < 1)
+    per_cu = 1;
+  const uint64_t resident = (uint64_t)(cus > 0 ? cus : 256) * (uint64_t)per_cu;
+  const uint64_t want = ((uint64_t)njobs + per_block - 1) / per_block;
+  return (uint32_t)std::min(want, resident);
+}
+
+template <int G>
+static hipError_t launch_hash_chain_group_ckpt_shape(const efes_job* jobs, uint32_t njobs, void* scratch,
+                                                     const Tables* tabs, int cus, efes_checkpoint* const* ckpt,
+                                                     hipStream_t s) {
+  const uint32_t grid = chain_ckpt_grid(hash_chain_group_ckpt_kernel<G>, njobs, (uint64_t)kDeepWaves * (64 / G), cus);
+  clear_last_error();
+  hipLaunchKernelGGL(hash_chain_group_ckpt_kernel<G>, dim3(grid), dim3(64 * kDeepWaves), 0, s, jobs, njobs, tabs,
+                     scratch, ckpt);
+  return hipGetLastError();
+}
+
+hipError_t launch_hash_chain_ckpt(const efes_job* jobs, uint32_t njobs, int G, efes_checkpoint* const* ckpt,
+                                  void* scratch, const Tables* tabs, int cus, hipStream_t s) {
+  if (njobs == 0) return hipSuccess;
+  if (G != 0 && G != 4 && G != 8 && G != 16 && G != 32) return hipErrorInvalidValue;
+  const hipError_t e = launch_hash_chain_prep(jobs, njobs, scratch, s);
+  if (e != hipSuccess) return e;
+  switch (G) {
+    case 0: {
+      const uint32_t grid = chain_ckpt_grid(hash_chain_ckpt_kernel, njobs, kDeepWaves, cus);
+      clear_last_error();
+      hipLaunchKernelGGL(hash_chain_ckpt_kernel, dim3(grid), dim3(64 * kDeepWaves), 0, s, jobs, njobs, tabs, scratch,
+                         ckpt);
+      return hipGetLastError();
+    }
+    case 4: return launch_hash_chain_group_ckpt_shape<4>(jobs, njobs, scratch, tabs, cus, ckpt, s);
+    case 8: return launch_hash_chain_group_ckpt_shape<8>(jobs, njobs, scratch, tabs, cus, ckpt, s);
+    case 16: return launch_hash_chain_group_ckpt_shape<16>(jobs, njobs, scratch, tabs, cus, ckpt, s);
+    default: return launch_hash_chain_group_ckpt_shape<32>(jobs, njobs, scratch, tabs, cus, ckpt, s);
+  }
+}
+
+// The `.info` text of n records (efes_checkpoints_marshal_text): one lane per byte of the 104 that
+// MarshalText encodes -- h big-endian, x as it lies, nx and len big-endian (sha1_efes.go:26-34), then the
+// CRC big-endian (crc32_efes.go:18-24) -- which it reads from the record and writes as two lower-case hex
+// characters.  efes_sha1_state_marshal_text / efes_crc32_state_marshal_text (efes_api.cpp) are the
+// specification.
+constexpr uint32_t kCkptTextBlock = 256;
+constexpr uint32_t kCkptBinBytes = EFES_CHECKPOINT_TEXT_BYTES / 2;  // 100 of the SHA-1 state + 4 of the CRC
+static_assert(kCkptBinBytes == 104 && (uint64_t)EFES_HASH_CHAIN_MAX_JOBS * kCkptBinBytes < (1ull << 32),
+              "checkpoint_text_kernel indexes the bytes with 32 bits");
+
+__global__ __launch_bounds__(kCkptTextBlock) void checkpoint_text_kernel(const efes_checkpoint* __restrict__ ckpt,
+                                                                         uint32_t n, char* __restrict__ text) {
+  const uint32_t t = blockIdx.x * kCkptTextBlock + threadIdx.x;
+  if (t >= n * kCkptBinBytes) return;
+  const uint32_t i = t / kCkptBinBytes, k = t - i * kCkptBinBytes;
+  uint32_t at;  // the byte of the record that MarshalText puts at position k
+  if (k < 20u) at = (k & ~3u) + (3u - (k & 3u));                                        // h[k / 4]
+  else if (k < 84u) at = (uint32_t)offsetof(efes_sha1_state, x) + (k - 20u);            // x
+  else if (k < 92u) at = (uint32_t)offsetof(efes_sha1_state, nx) + (7u - (k - 84u));    // nx
+  else if (k < 100u) at = (uint32_t)offsetof(efes_sha1_state, len) + (7u - (k - 92u));  // len
+  else at = (uint32_t)offsetof(efes_checkpoint, crc32) + (3u - (k - 100u));             // crc
+  const uint32_t b = reinterpret_cast<const uint8_t*>(ckpt + i)[at];
+  const uint32_t hi = b >> 4, lo = b & 15u;
+  char* out = text + (size_t)i * EFES_CHECKPOINT_TEXT_BYTES + 2u * k;
+  out[0] = (char)(hi < 10u ? '0' + hi : 'a' + (hi - 10u));
+  out[1] = (char)(lo < 10u ? '0' + lo : 'a' + (lo - 10u));
+}
+
+hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t total = n * kCkptBinBytes;
+  clear_last_error();
+  hipLaunchKernelGGL(checkpoint_text_kernel, dim3((total + kCkptTextBlock - 1) / kCkptTextBlock), dim3(kCkptTextBlock),
+                     0, s, ckpt, n, text);
+  return hipGetLastError();
 }
 
 }  // namespace efes

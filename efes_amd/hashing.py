@@ -148,6 +148,22 @@ class Context:
         check(lib().efes_hash_chain_mode(self.handle, jobs_ptr, njobs, scratch_ptr, scratch_bytes, stream, mode),
               "efes_hash_chain_mode")
 
+    def hash_chain_checkpoints(self, jobs_ptr: int, njobs: int, ckpt_ptr: int, scratch_ptr: int, scratch_bytes: int,
+                               stream: int | None, mode: int) -> None:
+        """efes_hash_chain_checkpoints: hash_chain_mode() that also leaves the resumable state after every
+        member that asks for one -- ckpt_ptr is a device array of njobs device pointers to 112-byte
+        records (CHECKPOINT_DTYPE; 0: none for that job), each written with the chain's SHA-1 state and
+        CRC after that member's Write.  Everything else as hash_chain_mode(), byte for byte."""
+        check(lib().efes_hash_chain_checkpoints(self.handle, jobs_ptr, njobs, ckpt_ptr, scratch_ptr, scratch_bytes,
+                                                stream, mode), "efes_hash_chain_checkpoints")
+
+    def checkpoints_marshal_text(self, ckpt_ptr: int, n: int, text_ptr: int, stream: int | None = None) -> None:
+        """efes_checkpoints_marshal_text: the `.info` texts of n contiguous device records at ckpt_ptr,
+        CHECKPOINT_TEXT_BYTES characters each at text_ptr (device): the 200 of the SHA-1 state's
+        MarshalText, then the 8 of the CRC's (asynchronous on `stream`)."""
+        check(lib().efes_checkpoints_marshal_text(self.handle, ckpt_ptr, n, text_ptr, stream),
+              "efes_checkpoints_marshal_text")
+
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""
         check(lib().efes_debug_fault_after(self.handle, k), "efes_debug_fault_after")

@@ -531,8 +531,10 @@ int efes_crc32_copy(efes_ctx* ctx, const efes_job* jobs_device, void* const* dst
  *     stale bytes x[nx:64], the sums, the statuses;
  *   - every member with EFES_JOB_FINALIZE gets its own 24-byte sum from the state after THAT member's
  *     Write: SHA-1 Sum on a copy (sha1.go:82-87), then the CRC big-endian -- the running digest of the
- *     object at that extent's end, what `.info` holds after each PATCH (fileinfo.go:10-58).  Members of
- *     length zero are allowed;
+ *     object at that extent's end.  For the CRC that is what `.info` holds after each PATCH
+ *     (fileinfo.go:10-58), since its state is its sum; for SHA-1 `.info` holds the marshalled STATE
+ *     (sha1_efes.go:25-38), which a 20-byte Sum cannot be resumed from: efes_hash_chain_checkpoints
+ *     (below) leaves that state after every member.  Members of length zero are allowed;
  *   - after the call the states hold what they hold after the valid members' Writes in order (h, x
  *     with its stale bytes, nx, len, crc); whether intermediate values are stored on the way is
  *     unspecified;
@@ -604,6 +606,77 @@ int efes_hash_chain(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, 
 int efes_hash_chain_mode(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs, void* scratch_device,
                          size_t scratch_bytes, void* stream, int mode);
 int efes_hash_chain_auto_mode(const efes_ctx* ctx, uint32_t nchains);
+
+/* Checkpoints: the RESUMABLE state of a chain after every member the caller asks for, what `.info` holds
+ * after each PATCH (fileinfo.go:10-58): the marshalled SHA-1 state (sha1_efes.go:25-38: h, all 64 bytes
+ * of x, nx, len) and the CRC (crc32_efes.go:18-24).  efes_hash_chain(_mode) leaves a chain's state only
+ * after its LAST member; a member's FINALIZE sum is a Sum on a copy, which nothing resumes from. */
+typedef struct efes_checkpoint {
+    efes_sha1_state sha1;   /* 104 bytes: h, x (all 64 bytes, stale ones included), _pad, nx, len */
+    efes_crc32_state crc32; /* 4 */
+    uint32_t _pad;          /* 0 */
+} efes_checkpoint;          /* 112 bytes, 8-byte aligned */
+#define EFES_CHECKPOINT_TEXT_BYTES 208 /* 200 (sha1_efes.go:25-38) + 8 (crc32_efes.go:18-24), no NUL */
+
+/* efes_hash_chain_mode that also leaves checkpoints.  It takes over that call's whole contract -- the
+ * job array, the chain and validity rules, the statuses, the final states, the per-member sums, the
+ * scratch (efes_hash_chain_scratch(njobs)), njobs <= EFES_HASH_CHAIN_MAX_JOBS, no host read-back,
+ * allocation or wait -- and everything efes_hash_chain_mode(mode) writes it writes byte for byte the same.
+ * mode is EFES_MODE_DEEP (wave walk) or EFES_MODE_GROUP4/8/16/32 (grouped walk); every other value,
+ * EFES_MODE_AUTO included, returns EFES_ERR_ARG.
+ * ckpt_device: a device array of njobs device pointers, parallel to jobs_device (as dst_device of
+ * efes_crc32_copy); ckpt[j] == NULL asks for no checkpoint of member j.  A NULL ckpt_device with
+ * njobs > 0 returns EFES_ERR_ARG; njobs == 0 returns EFES_OK and launches nothing; the other argument
+ * errors are those of efes_hash_chain_mode.
+ *   - member j gets its checkpoint when its Write took effect -- status EFES_OK, or EFES_ERR_STATE raised
+ *     at its Sum (sha1.go:107-109), where the state is written -- and it does not carry
+ *     EFES_JOB_SUM_ONLY.  Then all 112 bytes of *ckpt[j] are written: sha1 = the chain's SHA-1 state after
+ *     THAT member's Write, exactly what *job.sha1 would hold had the call ended there (h, all 64 bytes of
+ *     x with their stale bytes, nx, len; _pad 0), all zero bytes for a chain with sha1 == NULL;
+ *     crc32.crc = the CRC after that member's Write, 0 for a chain with crc32 == NULL; _pad = 0.  The
+ *     yardstick is that of the chain calls: j + 1 successive efes_hash_submit_mode(EFES_MODE_DEEP) calls of
+ *     one job each, the states read back after the last;
+ *   - nothing is written to *ckpt[j] for a member with status EFES_ERR_ARG, for a member whose Write
+ *     panics in Go (nx > 64: EFES_ERR_STATE from the Write) and for an EFES_JOB_SUM_ONLY job.  No byte
+ *     outside the 112 bytes of a due checkpoint is ever written through ckpt;
+ *   - the caller's contract, not checked: the records are 8-byte aligned and overlap neither each other
+ *     nor the states, sums, statuses, job array, pointer array, scratch or data; they are visible to
+ *     later work in stream order;
+ *   - resuming: a later call (any of the job or chain calls) whose head job does not carry EFES_JOB_INIT
+ *     and names states that are copies of ckpt[j].sha1 / ckpt[j].crc32 goes on as the uncut Writes do.
+ * The records are stored by kernels of their own (the two walks with one more step where a member ends:
+ * the state the walk has stored is read back behind the walk's own fence; DESIGN.md §4 "Chained SHA-1 +
+ * CRC, checkpoints"); efes_hash_chain and efes_hash_chain_mode launch what they launched before.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/hash_chain_ckpt/bench.json, a record on EVERY extent, the mode that
+ * efes_hash_chain_auto_mode gives; DESIGN.md §4 "Chained SHA-1 + CRC, checkpoints" has the table; "steps +
+ * copies" = what gave these records before: one efes_hash_submit (AUTO) per extent step and one device copy
+ * of all states after each step):
+ *   - against efes_hash_chain_mode, the same call without the records (three runs of the
+ *     tool): within 0.6 % of its time, either way, on the two 1024-object shapes (DEEP) and on the
+ *     ragged 4096-object set (GROUP16), which is what that call's own repetitions differ by; 1.03 to 1.05
+ *     at 4096 objects x 16 x 64 KiB and at 4096 x 64 x 4 KiB (GROUP16), which is at or beyond the upper end
+ *     of that call's own spread there (its slowest repetition lies 2 to 5 % above its median): the
+ *     per-member fence, load and store show when members are short;
+ *   - objects of UNEQUAL extent counts or sizes: the checkpoint call, at 0.61 (1024 objects of 1-64 extents
+ *     of 4 KiB-1 MiB) and 0.74 to 0.75 (4096 objects of 1-16 extents of 4 KiB-256 KiB) of the steps + copies;
+ *   - objects of EQUAL extents: the steps + copies stay faster on the device where their 16 or 64 calls and
+ *     copies are no burden -- the checkpoint call takes 1.03 to 1.04 (1024 x 16 x 256 KiB), 1.14 to 1.15
+ *     (4096 x 16 x 64 KiB) and 1.41 to 1.42 times (4096 x 64 x 4 KiB) their time, as the chain calls
+ *     themselves do against the bare steps -- and the checkpoint call is ONE call;
+ *   - the text launch takes 7 to 44 us for 16 384 to 262 144 records, under 1 % of the call that made them.
+ *
+ * efes_checkpoints_marshal_text: the `.info` texts of n contiguous records, on the device.  Record i
+ * gives, at text_device + 208 i, the 200 lower-case hex characters efes_sha1_state_marshal_text gives for
+ * ckpt[i].sha1 and then the 8 that efes_crc32_state_marshal_text gives for ckpt[i].crc32; no NUL, nothing
+ * behind n * 208 characters is written.  Asynchronous on `stream`; n <= EFES_HASH_CHAIN_MAX_JOBS.
+ * EFES_ERR_ARG for a NULL ctx, a larger n, or a NULL pointer with n > 0; n == 0 returns EFES_OK and
+ * launches nothing.  Unmarshalling stays on the host (efes_sha1_state_unmarshal_text below). */
+int efes_hash_chain_checkpoints(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs,
+                                efes_checkpoint* const* ckpt_device, void* scratch_device, size_t scratch_bytes,
+                                void* stream, int mode);
+int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt_device, uint32_t n, char* text_device,
+                                  void* stream);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 

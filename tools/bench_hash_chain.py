@@ -22,6 +22,12 @@ one efes_hash_submit(AUTO) / efes_hash_submit_mode(DEEP) of the same array; 16 3
 seeded ragged set of 4096 objects of 1-16 extents of 4 KiB-256 KiB, longest object first.
 Before any rate is printed every path's status must be EFES_OK, the objects' 24-byte sums of all paths
 must be equal, and two objects per shape must match hashlib and zlib.
+
+    python tools/bench_hash_chain.py --checkpoints [--out PATH] [--seconds 1.0] [--shapes 0,1,2,3,4]
+
+is the checkpoint leg (main_checkpoints below): efes_hash_chain_checkpoints with a record on every extent
+against efes_hash_chain_mode and against the steps with a device copy of the states after each; it writes
+profiles/hash_chain_ckpt/bench.json and bench.log, with the engine clock of each path's last repetition.
 """
 from __future__ import annotations
 
@@ -81,12 +87,187 @@ def stats(total: int, dev: list[float]) -> dict:
             "GiB_per_s": round(total / med / 2**30, 2)}
 
 
+def packed_shape(nobj: int, next_: int, size: int):
+    """equal_shape over the front of the pool only."""
+    return [[((i * next_ + k) * size, size) for k in range(next_)] for i in range(nobj)]
+
+
+CKPT_SHAPES = [SHAPES[2], SHAPES[0], SHAPES[3], SHAPES[6],
+               ("4096 objects x 64 extents x 4 KiB", lambda: packed_shape(4096, 64, 4 << 10))]
+
+
+def main_checkpoints(args) -> int:
+    """The --checkpoints leg: the resumable state after EVERY extent, three ways, on the shapes of CKPT_SHAPES.
+      ckpt         -- one efes_hash_chain_checkpoints call, a record per extent, at the mode
+                      efes_hash_chain_auto_mode gives for the object count;
+      mode         -- the same array through efes_hash_chain_mode at that mode: the call without the records;
+      steps-copies -- what a caller does today for the same records: one efes_hash_submit (AUTO) per extent
+                      step and one device copy of all states (SHA-1 and CRC, one buffer) after each step;
+      text         -- separately, efes_checkpoints_marshal_text over all records of the shape.
+    Before any rate: every status EFES_OK, the sums of all paths equal, every record of ckpt equal to the state
+    steps-copies copied after that extent's step, two objects equal to hashlib and zlib, and the texts of the
+    first and last record equal to the host codecs."""
+    import ctypes
+
+    import torch
+
+    from bench_crc_batch import Probe
+    from efes_amd import _lib
+    from efes_amd.hashing import default_context, hash_chain_auto_mode, hash_chain_scratch
+
+    FIN, INIT, CHAIN = _lib.EFES_JOB_FINALIZE, _lib.EFES_JOB_INIT, _lib.EFES_JOB_CHAIN
+    REC, TEXT = _lib.CHECKPOINT_DTYPE.itemsize, _lib.CHECKPOINT_TEXT_BYTES
+    mode_name = {v: k for k, v in {"DEEP": _lib.MODE_DEEP, **{"GROUP%d" % g: m for g, m in _lib.MODE_GROUP.items()}}.items()}
+    chosen = {int(x) for x in args.shapes.split(",")}
+    ctx = default_context(0)
+    probe = Probe()
+    stream = torch.cuda.Stream(device="cuda:0")
+    s = stream.cuda_stream
+    buf = torch.empty(POOL, dtype=torch.uint8, device="cuda:0")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    log = open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "bench.log"), "w")
+    results = []
+    for si, (name, make) in enumerate(CKPT_SHAPES):
+        if si not in chosen:
+            continue
+        objects = make()
+        nobj = len(objects)
+        counts = np.array([len(o) for o in objects], dtype=np.int64)
+        n, steps = int(counts.sum()), int(counts.max())
+        total = int(sum(m for o in objects for _, m in o))
+        owner = np.repeat(np.arange(nobj, dtype=np.uint64), counts)
+        step = np.concatenate([np.arange(c, dtype=np.int64) for c in counts])
+        ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
+        last = step == counts[owner.astype(np.int64)] - 1
+        mode = hash_chain_auto_mode(nobj, ctx)
+        with torch.cuda.stream(stream):
+            ctx.fill_synthetic(buf.data_ptr(), POOL, 0x5A1C + si, s)
+            # one buffer per path: nobj SHA-1 states, then nobj CRCs, so that steps-copies copies both at once
+            res = {p: dict(st=torch.zeros(nobj * 108, dtype=torch.uint8, device="cuda:0"),
+                           sums=torch.zeros(nobj * 24, dtype=torch.uint8, device="cuda:0"),
+                           status=torch.full((n,), -99, dtype=torch.int32, device="cuda:0")) for p in ("ckpt", "mode", "steps-copies")}
+
+            def job_array(r, order, chained):
+                j = np.zeros(n, dtype=_lib.JOB_DTYPE)
+                j["data"] = np.uint64(buf.data_ptr()) + ext[:, 0]
+                j["length"] = ext[:, 1]
+                j["sha1"] = np.uint64(r["st"].data_ptr()) + owner * np.uint64(104)
+                j["crc32"] = np.uint64(r["st"].data_ptr() + 104 * nobj) + owner * np.uint64(4)
+                j["sum"] = np.uint64(r["sums"].data_ptr()) + owner * np.uint64(24)  # FINALIZE on the last extent only
+                j["status"] = np.uint64(r["status"].data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(4)
+                j["flags"] = np.where(step == 0, INIT, CHAIN if chained else 0).astype(np.uint32) | np.where(last, FIN, 0).astype(np.uint32)
+                return torch.from_numpy(j[order].view(np.uint8).copy()).to("cuda:0")
+
+            by_step = np.argsort(step, kind="stable")
+            first_of_step = np.searchsorted(step[by_step], np.arange(steps + 1))
+            jobs = {"ckpt": job_array(res["ckpt"], np.arange(n), True), "mode": job_array(res["mode"], np.arange(n), True),
+                    "steps-copies": job_array(res["steps-copies"], by_step, False)}
+            scratch = torch.empty(hash_chain_scratch(n), dtype=torch.uint8, device="cuda:0")
+            recs = torch.zeros(n * REC, dtype=torch.uint8, device="cuda:0")
+            at = np.uint64(recs.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(REC)
+            ptrs = torch.from_numpy(at.view(np.uint8).copy()).to("cuda:0")
+            snaps = torch.zeros((steps, nobj * 108), dtype=torch.uint8, device="cuda:0")
+            text = torch.zeros(n * TEXT, dtype=torch.uint8, device="cuda:0")
+        stream.synchronize()
+
+        def run_ckpt():
+            ctx.hash_chain_checkpoints(jobs["ckpt"].data_ptr(), n, ptrs.data_ptr(), scratch.data_ptr(), scratch.numel(), s, mode)
+
+        def run_mode():
+            ctx.hash_chain_mode(jobs["mode"].data_ptr(), n, scratch.data_ptr(), scratch.numel(), s, mode)
+
+        def run_steps_copies():
+            base = jobs["steps-copies"].data_ptr()
+            for k in range(steps):
+                a, b = int(first_of_step[k]), int(first_of_step[k + 1])
+                ctx.submit(base + 56 * a, b - a, s, _lib.MODE_AUTO)
+                snaps[k].copy_(res["steps-copies"]["st"], non_blocking=True)
+
+        def run_text():
+            ctx.checkpoints_marshal_text(recs.data_ptr(), n, text.data_ptr(), s)
+
+        paths = {"ckpt": run_ckpt, "mode": run_mode, "steps-copies": run_steps_copies, "text": run_text}
+        dev, clock = {p: [] for p in paths}, {}
+        with torch.cuda.stream(stream):
+            for rep in range(20000):
+                todo = [p for p in paths if rep < 2 or sum(dev[p][1:]) < (args.seconds if p != "text" else args.seconds / 10)]
+                if not todo:
+                    break
+                for p in todo:  # alternating; repetition 0 is the warm-up
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    marked = probe.mark(s, 0)
+                    e0.record(stream)
+                    paths[p]()
+                    e1.record(stream)
+                    marked = marked and probe.mark(s, 1)
+                    stream.synchronize()
+                    dev[p].append(e0.elapsed_time(e1) / 1e3)
+                    if marked:
+                        clock[p] = probe.read()
+        stream.synchronize()
+        # ---- correctness before any rate
+        sums = {p: res[p]["sums"].cpu().numpy().reshape(nobj, 24) for p in res}
+        for p in res:
+            assert (res[p]["status"].cpu().numpy() == 0).all(), (name, p)
+            assert (sums[p] == sums["ckpt"]).all(), (name, p)
+            assert (res[p]["st"].cpu().numpy() == res["ckpt"]["st"].cpu().numpy()).all(), (name, p)
+        for i in {0, nobj - 1}:
+            data = b"".join(bytes(buf[a:a + m].cpu().numpy()) for a, m in objects[i])
+            assert bytes(sums["ckpt"][i]) == hashlib.sha1(data).digest() + zlib.crc32(data).to_bytes(4, "big"), (name, i)
+        got = recs.cpu().numpy().view(_lib.CHECKPOINT_DTYPE)
+        snap = snaps.cpu().numpy()
+        own = owner.astype(np.int64)
+        want_sha = snap[:, :104 * nobj].reshape(steps, nobj, 104)[step, own].copy().view(_lib.SHA1_STATE_DTYPE).reshape(n)
+        want_crc = snap[:, 104 * nobj:].copy().view(np.uint32).reshape(steps, nobj)[step, own]
+        for f in ("h", "x", "nx", "len"):
+            assert (got["sha1"][f] == want_sha[f]).all(), (name, "record", f)
+        assert (got["crc"] == want_crc).all() and (got["_pad"] == 0).all() and (got["sha1"]["_pad"] == 0).all(), (name, "record")
+        texts = text.cpu().numpy().reshape(n, TEXT)
+        for j in (0, n - 1):
+            raw = got[j].tobytes()
+            a, b = ctypes.create_string_buffer(200), ctypes.create_string_buffer(8)
+            _lib.lib().efes_sha1_state_marshal_text(ctypes.byref(_lib.Sha1State.from_buffer_copy(raw[:104])), a)
+            _lib.lib().efes_crc32_state_marshal_text(ctypes.byref(_lib.Crc32State.from_buffer_copy(raw[104:108])), b)
+            assert bytes(texts[j]) == a.raw + b.raw, (name, "text", j)
+        row = {"shape": name, "objects": nobj, "jobs": n, "extent_steps": steps, "bytes": total, "mode": mode_name[mode],
+               "record_bytes": n * REC, "text_bytes": n * TEXT,
+               "paths": {p: {**stats(total, dev[p]), "engine_mhz": clock.get(p)} for p in paths}}
+        del row["paths"]["text"]["GiB_per_s"]  # not a pass over the data
+        c = row["paths"]["ckpt"]["device_seconds_median"]
+        row["ckpt_over_mode"] = round(c / row["paths"]["mode"]["device_seconds_median"], 4)
+        row["ckpt_over_steps_copies"] = round(c / row["paths"]["steps-copies"]["device_seconds_median"], 4)
+        row["mode_spread_min_max_over_median"] = row["paths"]["mode"]["spread_min_max_over_median"]
+        row["text_over_ckpt"] = round(row["paths"]["text"]["device_seconds_median"] / c, 4)
+        results.append(row)
+        for f in (sys.stdout, log):
+            print(json.dumps(row), file=f, flush=True)
+    out = {"tool": "tools/bench_hash_chain.py --checkpoints", "device": torch.cuda.get_device_name(0),
+           "build_id": _lib.lib().efes_build_id().decode(), "pool_bytes": POOL, "seconds_per_path": args.seconds,
+           "checks": "every status EFES_OK; all paths' sums and final states equal; every record equal to the state copied after "
+                     "that extent's step; two objects per shape equal hashlib and zlib; two texts per shape equal the host codecs",
+           "shapes": results}
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    log.close()
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hash_chain_group", "bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--seconds", type=float, default=1.0, help="device-timed work per path and shape")
-    ap.add_argument("--shapes", default="0,1,2,3,4,5,6")
+    ap.add_argument("--shapes", default=None)
+    ap.add_argument("--checkpoints", action="store_true",
+                    help="the checkpoint leg (efes_hash_chain_checkpoints): writes profiles/hash_chain_ckpt/bench.json")
     args = ap.parse_args()
+    if args.checkpoints:
+        args.out = args.out or os.path.join(ROOT, "profiles", "hash_chain_ckpt", "bench.json")
+        args.shapes = args.shapes or "0,1,2,3,4"
+        return main_checkpoints(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "hash_chain_group", "bench.json")
+    args.shapes = args.shapes or "0,1,2,3,4,5,6"
     chosen = {int(x) for x in args.shapes.split(",")}
 
     import torch
