@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_scratch
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -246,7 +246,10 @@ class DeviceObjects:
     walk (sha1=True only) chooses how efes_hash_chain walks the objects: None is efes_hash_chain itself,
     one wavefront per object; "auto" is efes_hash_chain_mode at the mode efes_hash_chain_auto_mode gives
     for the number of objects that have extents (the grouped walk beyond one object per SIMD); an
-    EFES_MODE_* constant is passed to efes_hash_chain_mode as it is.  The results are the same bytes.
+    EFES_MODE_* constant is passed to efes_hash_chain_mode as it is.  "wide" submits through
+    efes_hash_chain_wide, one object per lane, for very many objects of short extents; "auto_wide" does so
+    where efes_hash_chain_auto_mode_wide gives EFES_MODE_WIDE for the number of objects that have extents,
+    and is "auto" below that.  The results are the same bytes.
 
     copy_to (CRC-only sets) also gathers the objects, in the pass that hashes them, through
     efes_crc32_copy: each object's extents are written one behind the other, in the object's byte order,
@@ -256,7 +259,8 @@ class DeviceObjects:
 
     checkpoints=True (sha1=True only; a CRC-only set's running CRCs already are its checkpoints) also
     keeps one 112-byte record per extent, contiguous in extent order, and always submits through
-    efes_hash_chain_checkpoints -- at the mode `walk` gives ("auto" as above), EFES_MODE_DEEP without one.
+    efes_hash_chain_checkpoints -- at the mode `walk` gives ("auto" as above), EFES_MODE_DEEP without one --
+    or, with the wide walk, through efes_hash_chain_wide with its record pointers.
     checkpoints_host() is the records (the resumable SHA-1 state and the CRC after each extent),
     checkpoint_texts() their `.info` texts, marshalled on the device.
     """
@@ -322,7 +326,7 @@ class DeviceObjects:
         else:
             jobs["flags"][self.last[counts > 0]] |= EFES_JOB_FINALIZE
         self.running = bool(running)
-        self.walk = hash_chain_auto_mode(int((counts > 0).sum()), self.ctx) if walk == "auto" else walk
+        self.wide, self.walk = self._resolve_walk(walk, int((counts > 0).sum()))
         self.jobs_host = jobs
         self.jobs = torch.from_numpy(jobs.view(np.uint8).copy()).to(device) if n else torch.zeros(56, dtype=torch.uint8, device=device)
         self.has_checkpoints = bool(checkpoints)
@@ -359,7 +363,27 @@ class DeviceObjects:
             if self.has_sha1:
                 self.states.copy_(self._init_states_dev)
 
+    def _resolve_walk(self, walk, nchains: int):
+        """(wide, mode) of a walk= argument: wide says that submit() calls efes_hash_chain_wide; otherwise mode
+        goes to efes_hash_chain_mode (None: efes_hash_chain itself).  An EFES_MODE_* constant passes as it is,
+        EFES_MODE_WIDE included, which efes_hash_chain_mode refuses."""
+        if not isinstance(walk, str):
+            return False, walk
+        if walk == "wide":
+            return True, MODE_WIDE
+        if walk == "auto_wide":
+            mode = hash_chain_auto_mode_wide(nchains, self.ctx)
+            return mode == MODE_WIDE, mode
+        if walk == "auto":
+            return False, hash_chain_auto_mode(nchains, self.ctx)
+        raise ValueError(f"DeviceObjects: walk={walk!r}")
+
     def submit(self) -> None:
+        if self.wide:
+            ckpt = self._ckpt_ptrs.data_ptr() if self.has_checkpoints else None
+            self._ordered(lambda stream: self.ctx.hash_chain_wide(self.jobs.data_ptr(), self.n, ckpt, self._scratch.data_ptr(),
+                                                                  self._scratch.numel(), stream))
+            return
         if self.has_checkpoints:
             self._ordered(lambda stream: self.ctx.hash_chain_checkpoints(self.jobs.data_ptr(), self.n, self._ckpt_ptrs.data_ptr(),
                                                                          self._scratch.data_ptr(), self._scratch.numel(),

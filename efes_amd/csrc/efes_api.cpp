@@ -446,6 +446,30 @@ int efes_hash_chain_checkpoints(efes_ctx* ctx, const efes_job* jobs, uint32_t nj
       efes::launch_hash_chain_ckpt(jobs, njobs, lanes, ckpt, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
 }
 
+int efes_hash_chain_wide(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, efes_checkpoint* const* ckpt,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+  if (!ctx || (!jobs && njobs) || njobs > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::hash_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(
+      efes::launch_hash_chain_wide(jobs, njobs, ckpt, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
+}
+
+// The wide walk from 32 chains per SIMD upwards (32 768 on 256 CUs): the smallest measured chain count from
+// which efes_hash_chain_wide's median stays below the minimum of efes_hash_chain_mode at
+// efes_hash_chain_auto_mode's mode (profiles/hash_chain_wide/bench.json; DESIGN.md §4 "Chained SHA-1 + CRC,
+// wide walk").  Measured at 4096, 16 384, 32 768, 65 536 and 262 144 chains: the wide walk also wins at 4096
+// chains of 64 x 4 KiB, but loses at 16 384 x 4 x 64 KiB, so below 32 768 the count alone does not decide.
+static constexpr uint64_t kChainWideFrom = 32;  // chains per SIMD
+
+int efes_hash_chain_auto_mode_wide(const efes_ctx* ctx, uint32_t nchains) {
+  const uint64_t simds = 4ull * (ctx ? (uint64_t)ctx->cus : 256ull);
+  if ((uint64_t)nchains >= kChainWideFrom * simds) return EFES_MODE_WIDE;
+  return efes_hash_chain_auto_mode(ctx, nchains);
+}
+
 int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, uint32_t n, char* text, void* stream) {
   if (!ctx || n > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
   if (n == 0) return EFES_OK;

@@ -174,6 +174,12 @@ hipError_t launch_hash_chain_group(const efes_job* jobs, uint32_t njobs, int G, 
 // walk; kernels of their own that also store ckpt[j] after every member that is due a record.
 hipError_t launch_hash_chain_ckpt(const efes_job* jobs, uint32_t njobs, int G, efes_checkpoint* const* ckpt,
                                   void* scratch, const Tables* tabs, int cus, hipStream_t s);
+// The two prep launches of every chain walk: the chains' heads listed in the scratch, the ticket zeroed.
+hipError_t launch_hash_chain_prep(const efes_job* jobs, uint32_t njobs, void* scratch, hipStream_t s);
+// The wide walk (efes_hash_chain_wide, efes_chain_wide.hip): the same prep launches and scratch, then a persistent launch with
+// one chain per lane; ckpt == NULL for no records, else as launch_hash_chain_ckpt's.
+hipError_t launch_hash_chain_wide(const efes_job* jobs, uint32_t njobs, efes_checkpoint* const* ckpt, void* scratch,
+                                  const Tables* tabs, int cus, hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 

@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -72,6 +72,13 @@ def hash_chain_auto_mode(nchains: int, ctx: "Context | None" = None) -> int:
     (host-only; without a context one MI355X is assumed): MODE_DEEP up to one chain per SIMD, then the
     grouped walk with as many lanes per chain as still hold every chain at once."""
     return int(lib().efes_hash_chain_auto_mode(ctx.handle if ctx else None, nchains))
+
+
+def hash_chain_auto_mode_wide(nchains: int, ctx: "Context | None" = None) -> int:
+    """efes_hash_chain_auto_mode_wide: hash_chain_auto_mode() for a caller that also has hash_chain_wide():
+    MODE_WIDE from the measured chain count upwards (that result goes to hash_chain_wide()), else what
+    hash_chain_auto_mode() gives (that goes to hash_chain_mode()).  Host-only."""
+    return int(lib().efes_hash_chain_auto_mode_wide(ctx.handle if ctx else None, nchains))
 
 
 class Context:
@@ -156,6 +163,14 @@ class Context:
         CRC after that member's Write.  Everything else as hash_chain_mode(), byte for byte."""
         check(lib().efes_hash_chain_checkpoints(self.handle, jobs_ptr, njobs, ckpt_ptr, scratch_ptr, scratch_bytes,
                                                 stream, mode), "efes_hash_chain_checkpoints")
+
+    def hash_chain_wide(self, jobs_ptr: int, njobs: int, ckpt_ptr: int | None, scratch_ptr: int, scratch_bytes: int,
+                        stream: int | None = None) -> None:
+        """efes_hash_chain_wide: hash_chain() by the wide walk, one chain per lane, for very many chains of
+        short members.  The arguments in the C call's order; ckpt_ptr None (NULL): no records; else a device array of njobs record pointers as
+        for hash_chain_checkpoints().  The same bytes as hash_chain() / hash_chain_checkpoints(MODE_DEEP)."""
+        check(lib().efes_hash_chain_wide(self.handle, jobs_ptr, njobs, ckpt_ptr, scratch_ptr, scratch_bytes, stream),
+              "efes_hash_chain_wide")
 
     def checkpoints_marshal_text(self, ckpt_ptr: int, n: int, text_ptr: int, stream: int | None = None) -> None:
         """efes_checkpoints_marshal_text: the `.info` texts of n contiguous device records at ckpt_ptr,

@@ -678,6 +678,61 @@ int efes_hash_chain_checkpoints(efes_ctx* ctx, const efes_job* jobs_device, uint
 int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt_device, uint32_t n, char* text_device,
                                   void* stream);
 
+/* efes_hash_chain by the WIDE walk: one chain per LANE, for very many chains of short members (tens of
+ * thousands to a million objects of a few PATCH-sized extents).  It takes over the whole contract of
+ * efes_hash_chain -- the job array, EFES_JOB_CHAIN / INIT / FINALIZE / SUM_ONLY and every validity rule, a
+ * status for every member (EFES_ERR_STATE exactly where the job kernels raise it), the final states with
+ * their stale bytes x[nx:64] (_pad left alone), a 24-byte sum for every FINALIZE member, members of length
+ * zero, chains with sha1 or crc32 NULL, njobs <= EFES_HASH_CHAIN_MAX_JOBS, the argument errors, the scratch
+ * (efes_hash_chain_scratch(njobs), so one buffer serves every chain call of a stream), no host read-back,
+ * allocation or wait -- and writes byte for byte what efes_hash_chain writes for every job array.
+ * ckpt_device: NULL for no checkpoints (unlike efes_hash_chain_checkpoints, which refuses NULL: this is one
+ * call for both uses); else a device array of njobs record pointers under the contract of
+ * efes_hash_chain_checkpoints -- all 112 bytes when the member's Write took effect and it is not
+ * EFES_JOB_SUM_ONLY, zeros for a hash the chain does not keep and for _pad, nothing for EFES_ERR_ARG, for a
+ * panicking Write or for ckpt[j] == NULL, no byte outside a due record -- and the records are byte for byte
+ * those of efes_hash_chain_checkpoints(EFES_MODE_DEEP).
+ * After the two prep launches of the chain calls a persistent launch of the WIDE job kernel's workgroup
+ * runs: a wavefront draws 64 consecutive chains, lane l walks chain t + l, and the wavefront goes through
+ * the members in rounds (round r = every lane's r-th member) as the WIDE job kernel goes through jobs.  The
+ * state stays in registers and LDS between members and is stored once per chain.  A wavefront lasts as
+ * long as the sum over rounds of its longest member, so arrays sorted longest first suit it, and so do
+ * chains of equal extent counts (DESIGN.md §4 "Chained SHA-1 + CRC, wide walk").
+ * efes_hash_chain_mode and efes_hash_chain_checkpoints keep refusing EFES_MODE_WIDE, and
+ * efes_hash_chain_auto_mode keeps its values.  efes_hash_chain_auto_mode_wide (host-only; ctx may be NULL:
+ * 256 CUs) is for a caller that has both: EFES_MODE_WIDE from the measured chain count upwards -- that
+ * result goes to efes_hash_chain_wide -- and efes_hash_chain_auto_mode's value below it, which goes to
+ * efes_hash_chain_mode.
+ * EFES_ABI_VERSION stays 8; a binding detects the two calls by their symbols.
+ * Which path when, continued (measured, profiles/hash_chain_wide/bench.json; DESIGN.md §4 "Chained SHA-1 +
+ * CRC, wide walk" has the table; fused jobs, medians of device time; "grouped walk" = efes_hash_chain_mode at
+ * efes_hash_chain_auto_mode's mode, "steps" as above):
+ *   - 32 768 objects and more, EQUAL extents (32 768 x 4 x 32 KiB, 65 536 x 4 x 16 KiB, 262 144 x 4 x 4 KiB):
+ *     the wide walk, at 0.43, 0.15 and 0.05 of the grouped walk's time (3.1, 1.6 and 1.7 ms for 4 GiB against
+ *     7.3, 10.7 and 32.0).  It equals the steps at 32 768 objects (1.00) and at 65 536 (0.97, inside both
+ *     spreads), and takes 0.79 of their time at 262 144; it is ONE call;
+ *   - 65 536 objects of UNEQUAL extents (1-8 extents of 4-64 KiB, longest first): the wide walk at 0.74 of
+ *     the grouped walk's time (15.4 ms against 20.9 for 9.5 GiB); the steps take 14.6 ms (the wide walk 1.06
+ *     times that, outside both spreads): a wavefront lasts as long as the sum over rounds of its longest
+ *     member;
+ *   - 16 384 objects x 4 x 64 KiB: the grouped walk; the wide walk takes 1.06 times its median (6.1 ms
+ *     against 5.8, minimum 5.4) with a quarter of the SIMDs holding a wavefront, the steps 4.6 ms;
+ *   - 4096 objects x 64 x 4 KiB: the wide walk takes 0.78 of the grouped walk's time (6.3 ms against 8.1)
+ *     although only 64 wavefronts have chains -- the grouped walk sends every short member through the
+ *     one-wave path -- and 1.14 times the steps' (5.5 ms).  efes_hash_chain_auto_mode_wide does not pick it
+ *     there: at 16 384 objects the wide walk loses, so below 32 768 the count alone does not decide;
+ *   - with a record on EVERY extent the wide walk takes 0.98 to 1.02 of its own time without (inside its
+ *     spread except at 4096 x 64 x 4 KiB: 1.015 with 262 144 records), so against efes_hash_chain_checkpoints and the steps + copies the ratios are
+ *     those above: 0.41, 0.15, 0.06, 0.73 and 0.75 of the checkpoint call on the five shapes it wins, 1.00 at
+ *     16 384 objects.
+ * efes_hash_chain_auto_mode_wide therefore returns EFES_MODE_WIDE from 32 chains per SIMD (32 768 on 256
+ * CUs), the smallest measured count from which the wide walk's median stays below the grouped walk's
+ * minimum. */
+int efes_hash_chain_wide(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs,
+                         efes_checkpoint* const* ckpt_device, void* scratch_device, size_t scratch_bytes,
+                         void* stream);
+int efes_hash_chain_auto_mode_wide(const efes_ctx* ctx, uint32_t nchains);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */

@@ -28,6 +28,13 @@ must be equal, and two objects per shape must match hashlib and zlib.
 is the checkpoint leg (main_checkpoints below): efes_hash_chain_checkpoints with a record on every extent
 against efes_hash_chain_mode and against the steps with a device copy of the states after each; it writes
 profiles/hash_chain_ckpt/bench.json and bench.log, with the engine clock of each path's last repetition.
+
+    python tools/bench_hash_chain.py --wide [--checkpoints] [--out PATH] [--seconds 1.0] [--shapes 0,1,2,3,4,5]
+
+is the wide-walk leg (main_wide below): efes_hash_chain_wide against efes_hash_chain_mode at
+efes_hash_chain_auto_mode's mode and against the steps, on many small objects; with --checkpoints also the
+three ways to a record on every extent, in the same run.  It writes profiles/hash_chain_wide/bench.json and
+bench.log.
 """
 from __future__ import annotations
 
@@ -254,6 +261,172 @@ def main_checkpoints(args) -> int:
     return 0
 
 
+WIDE_SHAPES = [SHAPES[5],
+               ("32768 objects x 4 extents x 32 KiB", lambda: equal_shape(32768, 4, 32 << 10)),
+               ("65536 objects x 4 extents x 16 KiB", lambda: equal_shape(65536, 4, 16 << 10)),
+               ("262144 objects x 4 extents x 4 KiB", lambda: equal_shape(262144, 4, 4 << 10)),
+               CKPT_SHAPES[4],
+               ("ragged: 65536 objects x 1-8 extents x 4 KiB-64 KiB, longest first",
+                lambda: ragged_shape(0x4A66EF, 65536, 8, 64 << 10))]
+
+
+def main_wide(args) -> int:
+    """The --wide leg, on the shapes of WIDE_SHAPES:
+      wide         -- (a) one efes_hash_chain_wide call, ckpt_device NULL;
+      mode         -- (b) efes_hash_chain_mode at the mode efes_hash_chain_auto_mode gives for the object count;
+      steps        -- (c) one efes_hash_submit (AUTO) per extent step, one job per object that still has an extent;
+    and with --checkpoints, in the same run:
+      wide-ckpt    -- (a') efes_hash_chain_wide with a record on every extent;
+      ckpt         -- (b') efes_hash_chain_checkpoints at that mode;
+      steps-copies -- (c') the steps plus one device copy of all states after each step.
+    Before any rate: every status EFES_OK, all paths' sums and final states equal, the records of wide-ckpt equal
+    to those of ckpt and to the states steps-copies copied, two objects per shape equal to hashlib and zlib."""
+    import torch
+
+    from bench_crc_batch import Probe
+    from efes_amd import _lib
+    from efes_amd.hashing import default_context, hash_chain_auto_mode, hash_chain_scratch
+
+    FIN, INIT, CHAIN = _lib.EFES_JOB_FINALIZE, _lib.EFES_JOB_INIT, _lib.EFES_JOB_CHAIN
+    REC = _lib.CHECKPOINT_DTYPE.itemsize
+    mode_name = {v: k for k, v in {"DEEP": _lib.MODE_DEEP, **{"GROUP%d" % g: m for g, m in _lib.MODE_GROUP.items()}}.items()}
+    chosen = {int(x) for x in args.shapes.split(",")}
+    names = ["wide", "mode", "steps"] + (["wide-ckpt", "ckpt", "steps-copies"] if args.checkpoints else [])
+    ctx = default_context(0)
+    probe = Probe()
+    stream = torch.cuda.Stream(device="cuda:0")
+    s = stream.cuda_stream
+    buf = torch.empty(POOL, dtype=torch.uint8, device="cuda:0")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    log = open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "bench.log"), "w")
+    results = []
+    for si, (name, make) in enumerate(WIDE_SHAPES):
+        if si not in chosen:
+            continue
+        objects = make()
+        nobj = len(objects)
+        counts = np.array([len(o) for o in objects], dtype=np.int64)
+        n, steps = int(counts.sum()), int(counts.max())
+        owner = np.repeat(np.arange(nobj, dtype=np.uint64), counts)
+        own = owner.astype(np.int64)
+        step = np.concatenate([np.arange(c, dtype=np.int64) for c in counts])
+        ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
+        total = int(ext[:, 1].sum())
+        last = step == counts[own] - 1
+        mode = hash_chain_auto_mode(nobj, ctx)
+        with torch.cuda.stream(stream):
+            ctx.fill_synthetic(buf.data_ptr(), POOL, 0x5A1C + 16 + si, s)
+            res = {p: dict(st=torch.zeros(nobj * 108, dtype=torch.uint8, device="cuda:0"),
+                           sums=torch.zeros(nobj * 24, dtype=torch.uint8, device="cuda:0"),
+                           status=torch.full((n,), -99, dtype=torch.int32, device="cuda:0")) for p in names}
+
+            def job_array(r, order, chained):
+                j = np.zeros(n, dtype=_lib.JOB_DTYPE)
+                j["data"] = np.uint64(buf.data_ptr()) + ext[:, 0]
+                j["length"] = ext[:, 1]
+                j["sha1"] = np.uint64(r["st"].data_ptr()) + owner * np.uint64(104)
+                j["crc32"] = np.uint64(r["st"].data_ptr() + 104 * nobj) + owner * np.uint64(4)
+                j["sum"] = np.uint64(r["sums"].data_ptr()) + owner * np.uint64(24)  # FINALIZE on the last extent only
+                j["status"] = np.uint64(r["status"].data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(4)
+                j["flags"] = np.where(step == 0, INIT, CHAIN if chained else 0).astype(np.uint32) | np.where(last, FIN, 0).astype(np.uint32)
+                return torch.from_numpy(j[order].view(np.uint8).copy()).to("cuda:0")
+
+            by_step = np.argsort(step, kind="stable")
+            first_of_step = np.searchsorted(step[by_step], np.arange(steps + 1))
+            jobs = {p: job_array(res[p], by_step if p.startswith("steps") else np.arange(n), not p.startswith("steps")) for p in names}
+            scratch = torch.empty(hash_chain_scratch(n), dtype=torch.uint8, device="cuda:0")
+            if args.checkpoints:
+                recs = {p: torch.zeros(n * REC, dtype=torch.uint8, device="cuda:0") for p in ("wide-ckpt", "ckpt")}
+                ptrs = {p: torch.from_numpy((np.uint64(recs[p].data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(REC))
+                                            .view(np.uint8).copy()).to("cuda:0") for p in recs}
+                snaps = torch.zeros((steps, nobj * 108), dtype=torch.uint8, device="cuda:0")
+        stream.synchronize()
+
+        def run_steps(p, copies):
+            base = jobs[p].data_ptr()
+            for k in range(steps):
+                a, b = int(first_of_step[k]), int(first_of_step[k + 1])
+                ctx.submit(base + 56 * a, b - a, s, _lib.MODE_AUTO)
+                if copies:
+                    snaps[k].copy_(res[p]["st"], non_blocking=True)
+
+        paths = {"wide": lambda: ctx.hash_chain_wide(jobs["wide"].data_ptr(), n, None, scratch.data_ptr(), scratch.numel(), s),
+                 "mode": lambda: ctx.hash_chain_mode(jobs["mode"].data_ptr(), n, scratch.data_ptr(), scratch.numel(), s, mode),
+                 "steps": lambda: run_steps("steps", False)}
+        if args.checkpoints:
+            paths["wide-ckpt"] = lambda: ctx.hash_chain_wide(jobs["wide-ckpt"].data_ptr(), n, ptrs["wide-ckpt"].data_ptr(),
+                                                             scratch.data_ptr(), scratch.numel(), s)
+            paths["ckpt"] = lambda: ctx.hash_chain_checkpoints(jobs["ckpt"].data_ptr(), n, ptrs["ckpt"].data_ptr(), scratch.data_ptr(),
+                                                               scratch.numel(), s, mode)
+            paths["steps-copies"] = lambda: run_steps("steps-copies", True)
+        dev, clock = {p: [] for p in paths}, {}
+        with torch.cuda.stream(stream):
+            for rep in range(20000):
+                todo = [p for p in paths if rep < 2 or sum(dev[p][1:]) < args.seconds]
+                if not todo:
+                    break
+                for p in todo:  # alternating; repetition 0 is the warm-up
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    marked = probe.mark(s, 0)
+                    e0.record(stream)
+                    paths[p]()
+                    e1.record(stream)
+                    marked = marked and probe.mark(s, 1)
+                    stream.synchronize()
+                    dev[p].append(e0.elapsed_time(e1) / 1e3)
+                    if marked:
+                        clock[p] = probe.read()
+        stream.synchronize()
+        # ---- correctness before any rate
+        sums = {p: res[p]["sums"].cpu().numpy().reshape(nobj, 24) for p in paths}
+        st0 = res["mode"]["st"].cpu().numpy()
+        for p in paths:
+            assert (res[p]["status"].cpu().numpy() == 0).all(), (name, p)
+            assert (sums[p] == sums["mode"]).all(), (name, p)
+            assert (res[p]["st"].cpu().numpy() == st0).all(), (name, p)
+        for i in {0, nobj - 1}:
+            data = b"".join(bytes(buf[a:a + m].cpu().numpy()) for a, m in objects[i])
+            assert bytes(sums["wide"][i]) == hashlib.sha1(data).digest() + zlib.crc32(data).to_bytes(4, "big"), (name, i)
+        if args.checkpoints:
+            got = recs["wide-ckpt"].cpu().numpy()
+            assert (got == recs["ckpt"].cpu().numpy()).all(), (name, "records")
+            got = got.view(_lib.CHECKPOINT_DTYPE)
+            snap = snaps.cpu().numpy()
+            want_sha = snap[:, :104 * nobj].reshape(steps, nobj, 104)[step, own].copy().view(_lib.SHA1_STATE_DTYPE).reshape(n)
+            want_crc = snap[:, 104 * nobj:].copy().view(np.uint32).reshape(steps, nobj)[step, own]
+            for f in ("h", "x", "nx", "len"):
+                assert (got["sha1"][f] == want_sha[f]).all(), (name, "record", f)
+            assert (got["crc"] == want_crc).all() and (got["_pad"] == 0).all() and (got["sha1"]["_pad"] == 0).all(), (name, "record")
+        row = {"shape": name, "objects": nobj, "jobs": n, "extent_steps": steps, "bytes": total, "mode": mode_name[mode],
+               "paths": {p: {**stats(total, dev[p]), "engine_mhz": clock.get(p)} for p in paths}}
+        P = row["paths"]
+        row["wide_over_mode"] = round(P["wide"]["device_seconds_median"] / P["mode"]["device_seconds_median"], 4)
+        row["wide_over_steps"] = round(P["wide"]["device_seconds_median"] / P["steps"]["device_seconds_median"], 4)
+        row["wide_median_below_mode_min"] = P["wide"]["device_seconds_median"] < P["mode"]["device_seconds_min"]
+        if args.checkpoints:
+            row["wide_ckpt_over_ckpt"] = round(P["wide-ckpt"]["device_seconds_median"] / P["ckpt"]["device_seconds_median"], 4)
+            row["wide_ckpt_over_steps_copies"] = round(P["wide-ckpt"]["device_seconds_median"] / P["steps-copies"]["device_seconds_median"], 4)
+            row["wide_ckpt_over_wide"] = round(P["wide-ckpt"]["device_seconds_median"] / P["wide"]["device_seconds_median"], 4)
+        results.append(row)
+        for f in (sys.stdout, log):
+            print(json.dumps(row), file=f, flush=True)
+        del res, jobs, scratch
+        if args.checkpoints:
+            del recs, ptrs, snaps
+    out = {"tool": "tools/bench_hash_chain.py --wide" + (" --checkpoints" if args.checkpoints else ""),
+           "device": torch.cuda.get_device_name(0), "build_id": _lib.lib().efes_build_id().decode(), "pool_bytes": POOL,
+           "seconds_per_path": args.seconds,
+           "checks": "every status EFES_OK; all paths' sums and final states equal; the wide walk's records equal to "
+                     "efes_hash_chain_checkpoints' and to the states copied after each step; two objects per shape equal hashlib and zlib",
+           "shapes": results}
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    log.close()
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -261,7 +434,13 @@ def main() -> int:
     ap.add_argument("--shapes", default=None)
     ap.add_argument("--checkpoints", action="store_true",
                     help="the checkpoint leg (efes_hash_chain_checkpoints): writes profiles/hash_chain_ckpt/bench.json")
+    ap.add_argument("--wide", action="store_true",
+                    help="the wide-walk leg (efes_hash_chain_wide): writes profiles/hash_chain_wide/bench.json")
     args = ap.parse_args()
+    if args.wide:
+        args.out = args.out or os.path.join(ROOT, "profiles", "hash_chain_wide", "bench.json")
+        args.shapes = args.shapes or "0,1,2,3,4,5"
+        return main_wide(args)
     if args.checkpoints:
         args.out = args.out or os.path.join(ROOT, "profiles", "hash_chain_ckpt", "bench.json")
         args.shapes = args.shapes or "0,1,2,3,4"
