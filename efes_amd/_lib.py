@@ -151,6 +151,7 @@ SIGNATURES = {
     "efes_pool_stats": (_I, [_VP, _U32, _P(QueueStats)]),
     "efes_pair_stats_get": (_I, [_P(PairStats)]),
     "efes_debug_fault_after": (_I, [_VP, _U64]),
+    "efes_debug_set_cus": (_I, [_VP, _I]),
     "efes_sha1_new": (_I, [_VP, _P(_VP)]),
     "efes_sha1_new_zero": (_I, [_VP, _P(_VP)]),
     "efes_sha1_free": (None, [_VP]),

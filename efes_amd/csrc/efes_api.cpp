@@ -140,11 +140,12 @@ void efes::build_pos_tables(const Tables* t, PosTables* out) {
 // A stream on a hardware queue of its own (efes_internal.hpp).
 hipError_t efes::own_queue_stream(const efes_ctx* ctx, hipStream_t* out) {
   uint32_t all_cus[8];
+  const int cus = ctx->device_cus;  // the device's own count: efes_debug_set_cus never narrows the mask
   for (int w = 0; w < 8; ++w) {
-    const int left = ctx->cus - 32 * w;
+    const int left = cus - 32 * w;
     all_cus[w] = left >= 32 ? 0xffffffffu : left > 0 ? (1u << left) - 1u : 0u;
   }
-  return hipExtStreamCreateWithCUMask(out, (uint32_t)std::min(8, (ctx->cus + 31) / 32), all_cus);
+  return hipExtStreamCreateWithCUMask(out, (uint32_t)std::min(8, (cus + 31) / 32), all_cus);
 }
 
 // efes_amd/build.py passes -DEFES_BUILD_ID="<source_id()>"; other builds (A/B variants, sanitizer
@@ -208,7 +209,7 @@ int efes_ctx_create(int device, efes_ctx** out) {
   if (!host) { delete ctx; return EFES_ERR_NOMEM; }
   efes::build_tables(host);
   efes::build_pos_tables(host, reinterpret_cast<efes::PosTables*>(host + 1));
-  ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  ctx->cus = ctx->device_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
   // The part streams of a planned batch are created by the first multi-part efes_hash_submit_plan
@@ -264,6 +265,13 @@ void efes_ctx_destroy(efes_ctx* ctx) {
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;
+}
+
+// Test hook (efes_testing.h): the launchers read ctx->cus at every call, so the next launch has the new grid.
+int efes_debug_set_cus(efes_ctx* ctx, int cus) {
+  if (!ctx || cus < 1 || cus > ctx->device_cus) return EFES_ERR_ARG;
+  ctx->cus = cus;
+  return EFES_OK;
 }
 
 int efes_ctx_device(const efes_ctx* ctx) { return ctx ? ctx->device : -1; }

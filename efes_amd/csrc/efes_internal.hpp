@@ -223,6 +223,7 @@ struct efes_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   int cus = 256;                  // compute units (efes_plan_batch's capacity)
+  int device_cus = 256;           // the device's own count: `cus` unless a test lowered it (efes_debug_set_cus)
   // streams of a planned batch's parts (efes_hash_submit_plan), one per part: never `stream`,
   // so a planned batch does not queue behind NULL-stream work of the context
   hipStream_t side[EFES_PLAN_MAX_PARTS] = {};

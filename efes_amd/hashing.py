@@ -183,6 +183,11 @@ class Context:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""
         check(lib().efes_debug_fault_after(self.handle, k), "efes_debug_fault_after")
 
+    def debug_set_cus(self, cus: int) -> None:
+        """Test hook (efes_debug_set_cus): this context's launchers size their grids for `cus` compute units,
+        1 <= cus <= the device's own count (which restores it).  Fewer workgroups, nothing else."""
+        check(lib().efes_debug_set_cus(self.handle, cus), "efes_debug_set_cus")
+
     def copy_to_host(self, dst_host: int, src_device: int, nbytes: int, stream: int | None = None) -> None:
         check(lib().efes_copy_to_host(self.handle, dst_host, src_device, nbytes, stream), "efes_copy_to_host")
 

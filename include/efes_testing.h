@@ -20,6 +20,10 @@ extern "C" {
  * Go surface (tests/test_gpu_boundary.py). */
 int efes_debug_fault_after(efes_ctx* ctx, uint64_t k);
 
+/* Lowers the compute-unit count ctx's launchers size their grids by (efes_ctx_create read it from the
+ * device): 1 <= cus <= the device's own count, which restores it.  Fewer workgroups, nothing else. */
+int efes_debug_set_cus(efes_ctx* ctx, int cus);
+
 #ifdef __cplusplus
 }
 #endif
