@@ -190,6 +190,7 @@ SIGNATURES = {
     "efes_hash_chain_checkpoints": (_I, [_VP, _VP, _U32, _VP, _VP, _S, _VP, _I]),
     "efes_hash_chain_wide": (_I, [_VP, _VP, _U32, _VP, _VP, _S, _VP]),
     "efes_hash_chain_auto_mode_wide": (_I, [_VP, _U32]),
+    "efes_hash_chain_wide_copy": (_I, [_VP, _VP, _VP, _VP, _U32, _VP, _S, _VP]),
     "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),

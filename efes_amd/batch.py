@@ -256,6 +256,9 @@ class DeviceObjects:
     starting at the device address copy_to + copy_offsets[i].  The default copy_offsets are those of
     default_copy_offsets(objects); .copy_offsets holds the offsets in use and .copy_bytes the room they
     need behind copy_to.  The destination must not overlap the source, the states or the sums.
+    With sha1=True only the wide walk copies: walk="wide" with copy_to gathers by the same layout rules
+    through efes_hash_chain_wide_copy (with crc32=False and with checkpoints=True too); every other walk,
+    "auto_wide" included, which may resolve to a grouped walk, raises ValueError.
 
     checkpoints=True (sha1=True only; a CRC-only set's running CRCs already are its checkpoints) also
     keeps one 112-byte record per extent, contiguous in extent order, and always submits through
@@ -273,8 +276,9 @@ class DeviceObjects:
                  copy_offsets=None, checkpoints: bool = False):
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
-        if copy_to is not None and sha1:
-            raise ValueError("DeviceObjects: copy_to= is CRC-only (efes_crc32_copy); build the set with sha1=False")
+        if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
+            raise ValueError('DeviceObjects: copy_to= with sha1=True needs walk="wide" (efes_hash_chain_wide_copy): no other '
+                             "walk copies; copy_to= is otherwise CRC-only (efes_crc32_copy): build the set with sha1=False")
         if copy_offsets is not None and copy_to is None:
             raise ValueError("DeviceObjects: copy_offsets= needs copy_to=")
         import torch
@@ -352,7 +356,8 @@ class DeviceObjects:
             within = before - before[self.first[owner.astype(np.int64)]] if n else before
             dst = np.uint64(copy_to) + self.copy_offsets[owner.astype(np.int64)] + within
             self._dst = torch.from_numpy(dst.astype(np.uint64).view(np.uint8).copy()).to(device) if n else torch.zeros(8, dtype=torch.uint8, device=device)
-            scratch_bytes = crc32_copy_scratch(n)
+            if not sha1:  # the wide walk with copy takes the chain calls' scratch
+                scratch_bytes = crc32_copy_scratch(n)
         self._scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=device)
         torch.cuda.synchronize(device)
 
@@ -381,6 +386,10 @@ class DeviceObjects:
     def submit(self) -> None:
         if self.wide:
             ckpt = self._ckpt_ptrs.data_ptr() if self.has_checkpoints else None
+            if self.copy_to is not None:
+                self._ordered(lambda stream: self.ctx.hash_chain_wide_copy(self.jobs.data_ptr(), self.n, self._dst.data_ptr(), ckpt,
+                                                                           self._scratch.data_ptr(), self._scratch.numel(), stream))
+                return
             self._ordered(lambda stream: self.ctx.hash_chain_wide(self.jobs.data_ptr(), self.n, ckpt, self._scratch.data_ptr(),
                                                                   self._scratch.numel(), stream))
             return

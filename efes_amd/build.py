@@ -13,9 +13,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libefeshash.so")
-SOURCES = ["efes_kernels.hip", "efes_chain_wide.hip", "efes_crc_span.hip", "efes_crc_batch.hip", "efes_api.cpp", "efes_ingest.cpp", "efes_queue.cpp",
+SOURCES = ["efes_kernels.hip", "efes_chain_wide.hip", "efes_chain_wide_copy.hip", "efes_crc_span.hip", "efes_crc_batch.hip", "efes_api.cpp", "efes_ingest.cpp", "efes_queue.cpp",
            "efes_stream.cpp", "efes_plan.cpp"]
-HEADERS = ["efes_internal.hpp", "efes_gf2.hpp", "sha1_device.hpp", "efes_wide_device.hpp"]
+HEADERS = ["efes_internal.hpp", "efes_gf2.hpp", "sha1_device.hpp", "efes_wide_device.hpp", "efes_chain_wide_device.hpp",
+           "efes_chain_wide_body.inc"]
 PUBLIC_HEADERS = ["efes_hash.h", "efes_testing.h"]
 ARCH = "gfx950"
 
@@ -109,6 +110,14 @@ def build_tools() -> list[str]:
         out.append(so)
     src = os.path.join(ROOT, "tools", "readprobe.hip")  # bench.py's read ceiling of the span leg's buffer
     so = os.path.join(ROOT, "tools", "libreadprobe.so")
+    if os.path.exists(src) and _stale(so, [src]):
+        subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", so + ".tmp"],
+                       check=True)
+        os.replace(so + ".tmp", so)
+    if os.path.exists(so):
+        out.append(so)
+    src = os.path.join(ROOT, "tools", "gathercopy.hip")  # bench_hash_chain_copy.py's plain gather of ragged extents
+    so = os.path.join(ROOT, "tools", "libgathercopy.so")
     if os.path.exists(src) and _stale(so, [src]):
         subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", so + ".tmp"],
                        check=True)

@@ -465,6 +465,18 @@ int efes_hash_chain_wide(efes_ctx* ctx, const efes_job* jobs, uint32_t njobs, ef
       efes::launch_hash_chain_wide(jobs, njobs, ckpt, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
 }
 
+int efes_hash_chain_wide_copy(efes_ctx* ctx, const efes_job* jobs, void* const* dst, efes_checkpoint* const* ckpt,
+                              uint32_t njobs, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!ctx || (!jobs && njobs) || njobs > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
+  if (njobs == 0) return EFES_OK;
+  if (!dst) return EFES_ERR_ARG;  // nothing to copy to: efes_hash_chain_wide
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) || scratch_bytes < efes::hash_chain_scratch_bytes(njobs))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(
+      efes::launch_hash_chain_wide_copy(jobs, dst, njobs, ckpt, scratch, ctx->d_tabs, ctx->cus, pick(ctx, stream)));
+}
+
 // The wide walk from 32 chains per SIMD upwards (32 768 on 256 CUs): the smallest measured chain count from
 // which efes_hash_chain_wide's median stays below the minimum of efes_hash_chain_mode at
 // efes_hash_chain_auto_mode's mode (profiles/hash_chain_wide/bench.json; DESIGN.md §4 "Chained SHA-1 + CRC,

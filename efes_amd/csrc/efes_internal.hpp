@@ -180,6 +180,11 @@ hipError_t launch_hash_chain_prep(const efes_job* jobs, uint32_t njobs, void* sc
 // one chain per lane; ckpt == NULL for no records, else as launch_hash_chain_ckpt's.
 hipError_t launch_hash_chain_wide(const efes_job* jobs, uint32_t njobs, efes_checkpoint* const* ckpt, void* scratch,
                                   const Tables* tabs, int cus, hipStream_t s);
+// The wide walk with copy (efes_hash_chain_wide_copy, efes_chain_wide_copy.hip): launch_hash_chain_wide with kernels
+// of their own that also store every member whose Write takes effect at dsts[job] (NULL: hashed, not copied).
+hipError_t launch_hash_chain_wide_copy(const efes_job* jobs, void* const* dsts, uint32_t njobs,
+                                       efes_checkpoint* const* ckpt, void* scratch, const Tables* tabs, int cus,
+                                       hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 

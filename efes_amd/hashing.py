@@ -172,6 +172,14 @@ class Context:
         check(lib().efes_hash_chain_wide(self.handle, jobs_ptr, njobs, ckpt_ptr, scratch_ptr, scratch_bytes, stream),
               "efes_hash_chain_wide")
 
+    def hash_chain_wide_copy(self, jobs_ptr: int, njobs: int, dst_ptr: int, ckpt_ptr: int | None, scratch_ptr: int,
+                             scratch_bytes: int, stream: int | None = None) -> None:
+        """efes_hash_chain_wide_copy: hash_chain_wide() that also copies every member whose Write takes effect, in
+        the pass that hashes it, to the device pointer dst[j] of the device array at dst_ptr (any alignment; 0:
+        hashed, not copied).  ckpt_ptr, the scratch and everything written as for hash_chain_wide()."""
+        check(lib().efes_hash_chain_wide_copy(self.handle, jobs_ptr, dst_ptr, ckpt_ptr, njobs, scratch_ptr, scratch_bytes,
+                                              stream), "efes_hash_chain_wide_copy")
+
     def checkpoints_marshal_text(self, ckpt_ptr: int, n: int, text_ptr: int, stream: int | None = None) -> None:
         """efes_checkpoints_marshal_text: the `.info` texts of n contiguous device records at ckpt_ptr,
         CHECKPOINT_TEXT_BYTES characters each at text_ptr (device): the 200 of the SHA-1 state's

@@ -733,6 +733,66 @@ int efes_hash_chain_wide(efes_ctx* ctx, const efes_job* jobs_device, uint32_t nj
                          void* stream);
 int efes_hash_chain_auto_mode_wide(const efes_ctx* ctx, uint32_t nchains);
 
+/* efes_hash_chain_wide that also GATHERS: every byte is written out and hashed by both digests in one pass
+ * -- io.MultiWriter(f, CRC32, Sha1) with a device destination as the first writer (filereceiver.go:208-209)
+ * -- for an upload whose PATCH-sized extents lie scattered over a staging pool and which is wanted
+ * contiguous for the write-out AND with its `.info` digests.
+ * The call is efes_hash_chain_wide plus a copy of each member's bytes.  It takes over that call's whole
+ * contract: the job array, EFES_JOB_CHAIN / INIT / FINALIZE / SUM_ONLY and every validity rule, a status for
+ * every member, the final states with their stale bytes, the per-member sums, ckpt_device with its
+ * NULL-means-no-records rule, the scratch (efes_hash_chain_scratch(njobs)), njobs <=
+ * EFES_HASH_CHAIN_MAX_JOBS, njobs == 0 returns EFES_OK and launches nothing, the argument errors, no host
+ * read-back, allocation or wait.  Everything efes_hash_chain_wide writes for a job array this call writes
+ * byte for byte the same.  The copy:
+ *   - dst_device is a device array of njobs device pointers, parallel to jobs_device.  dst[j] may have any
+ *     alignment, independent of the alignment of jobs[j].data; dst[j] == NULL: member j is hashed and not
+ *     copied.  A NULL dst_device with njobs > 0 returns EFES_ERR_ARG: use efes_hash_chain_wide;
+ *   - member j is copied when its Write took effect: status EFES_OK, or EFES_ERR_STATE raised at its Sum
+ *     (sha1.go:107-109, where the state is written too).  Then exactly [dst[j], dst[j] + length) holds the
+ *     source bytes.  A zero-length member writes nothing, and so does every EFES_JOB_SUM_ONLY job;
+ *   - nothing is written through dst[j] for a member with status EFES_ERR_ARG, for a member whose Write
+ *     panics in Go (nx > 64: EFES_ERR_STATE from the Write) and the members behind it, and for a job that
+ *     names neither state, which hashes nothing and copies nothing.  This is tighter than efes_crc32_copy,
+ *     which learns validity only after its scan: the wide walk knows it, lane by lane, before it touches
+ *     the member's bytes;
+ *   - no byte outside a due range is ever written and no destination byte is ever read: the ranges of a
+ *     gathered object abut at byte granularity and belong to other lanes and wavefronts, so partial pieces
+ *     are narrower stores, never read-modify-write;
+ *   - the caller's contract, not checked: destination ranges overlap neither each other nor any source
+ *     range, the states, sums, statuses, records, job array, pointer arrays or scratch;
+ *   - the destination bytes are visible to later work in stream order, like the states.
+ * The walk's kernels with three stores added (kernels of their own; efes_hash_chain_wide launches what it
+ * launched before): the bytes that complete a pending x[:nx] and the bytes behind the last whole block go
+ * out one by one, every whole block as four 16-byte stores from the registers it is hashed from, at
+ * whatever alignment the destination has (DESIGN.md §4 "Chained SHA-1 + CRC, wide walk with copy").
+ * EFES_ABI_VERSION stays 8; a binding detects the call by its symbol.
+ * Which path when, continued (measured, profiles/hash_chain_wide_copy/bench.json; DESIGN.md §4 "Chained
+ * SHA-1 + CRC, wide walk with copy" has the table; fused jobs, every object gathered contiguously, medians
+ * of device time; "two calls" = efes_hash_chain_wide, then the best single-launch copy of the same extents):
+ *   - 32 768 x 4 x 32 KiB, 65 536 x 4 x 16 KiB and the ragged 65 536 objects of 1-8 extents of 4-64 KiB:
+ *     efes_hash_chain_wide_copy, at 0.95, 0.85 and 0.87 of the two calls' time (4.5, 2.7 and 18.1 ms against 4.7,
+ *     3.2 and 20.9), its median below the two calls' minimum on all three.  The copy does NOT ride along free,
+ *     as it does for efes_crc32_copy: the call takes 1.43, 1.66 and 1.14 times efes_hash_chain_wide alone (3.1,
+ *     1.6 and 15.9 ms) and 2.8, 1.7 and 3.6 times the copy alone (1.6, 1.6 and 5.0 ms) -- a lane stores its
+ *     block as four 16-byte pieces into a line no other lane of the wavefront touches;
+ *   - 262 144 x 4 x 4 KiB: the TWO CALLS.  The fused call takes 1.09 times their time (3.3 ms against 3.0,
+ *     minimum 3.0) and twice efes_hash_chain_wide alone (1.7 ms); its median is not below their minimum;
+ *   - a record on every extent costs the fused call 1 % or less (0.99 to 1.01 of its time) except at 65 536 x
+ *     4 x 16 KiB, where it costs 10 %;
+ *   - relative misalignment is not free here: destinations displaced by 1 byte cost 1.32, 1.34, 1.26 and 1.14
+ *     times the aligned call on the four shapes, by 8 bytes 1.01, 1.30, 1.23 and 1.03 times.  A caller that
+ *     can choose keeps the objects' destinations 16-byte aligned (COPY_ALIGN does);
+ *   - efes_hash_chain_wide itself has not moved: its kernels are byte for byte the parent's, and its medians
+ *     lie within the spread of the parent's tree on the same machine on every shape;
+ *   - below the wide walk's range (fewer than 32 768 objects, or long extents) no fused walk is offered,
+ *     and none is needed.  Not measured, but from the rates above: the wave walk and the grouped walk hash
+ *     4 GiB in 5.8 to 32 ms, many times the 1.6 ms a copy of 4 GiB takes, so there the hash is many times
+ *     slower than the copy and a copy beside it costs a few per cent.  There the caller runs
+ *     efes_hash_chain(_mode) and a copy of its own. */
+int efes_hash_chain_wide_copy(efes_ctx* ctx, const efes_job* jobs_device, void* const* dst_device,
+                              efes_checkpoint* const* ckpt_device, uint32_t njobs, void* scratch_device,
+                              size_t scratch_bytes, void* stream);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */
