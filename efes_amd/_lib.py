@@ -92,6 +92,33 @@ class PairStats(ctypes.Structure):
                 ("settles", ctypes.c_uint64)]
 
 
+class Extent(ctypes.Structure):
+    """efes_extent: one extent of an object table (efes_objects_jobs)."""
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64)]
+
+
+class Objects(ctypes.Structure):
+    """efes_objects: an object table, a host struct of device addresses (host ones for efes_objects_jobs_host)."""
+    _fields_ = [("data", ctypes.c_void_p), ("extents", ctypes.c_void_p), ("first", ctypes.c_void_p),
+                ("sha1", ctypes.c_void_p), ("crc32", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("ckpt", ctypes.c_void_p), ("copy_to", ctypes.c_void_p),
+                ("copy_offsets", ctypes.c_void_p), ("nobjects", ctypes.c_uint32), ("nextents", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("copy_align", ctypes.c_uint32)]
+
+
+class ObjectsOut(ctypes.Structure):
+    """efes_objects_out: where efes_objects_jobs writes (jobs, dst[], ckpt[], layout)."""
+    _fields_ = [("jobs", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("ckpt", ctypes.c_void_p),
+                ("layout", ctypes.c_void_p)]
+
+
+EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING = 0x1, 0x2
+EFES_OBJECTS_MAX = EFES_HASH_CHAIN_MAX_JOBS
+EFES_OBJECTS_COPY_ALIGN = 256
+OBJECTS_SCAN_BLOCK = 1024  # kObjectsBlock of efes_objects.hip: lanes of one scan workgroup (the scans' seams)
+EXTENT_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8")])
+assert ctypes.sizeof(Extent) == 16 == EXTENT_DTYPE.itemsize and ctypes.sizeof(Objects) == 96 and ctypes.sizeof(ObjectsOut) == 32
+
 assert ctypes.sizeof(Sha1State) == 104 and ctypes.sizeof(Job) == 56 and ctypes.sizeof(QueueStats) == 32
 assert ctypes.sizeof(PairStats) == 32
 
@@ -191,6 +218,9 @@ SIGNATURES = {
     "efes_hash_chain_wide": (_I, [_VP, _VP, _U32, _VP, _VP, _S, _VP]),
     "efes_hash_chain_auto_mode_wide": (_I, [_VP, _U32]),
     "efes_hash_chain_wide_copy": (_I, [_VP, _VP, _VP, _VP, _U32, _VP, _S, _VP]),
+    "efes_objects_jobs_scratch": (_S, [_U32, _U32]),
+    "efes_objects_jobs": (_I, [_VP, _P(Objects), _P(ObjectsOut), _VP, _S, _VP]),
+    "efes_objects_jobs_host": (_I, [_P(Objects), _P(ObjectsOut)]),
     "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),

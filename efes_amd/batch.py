@@ -9,9 +9,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
-                   MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch
+from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
+                   MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Objects, ObjectsOut, Plan, PlanPart)
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -266,6 +266,14 @@ class DeviceObjects:
     or, with the wide walk, through efes_hash_chain_wide with its record pointers.
     checkpoints_host() is the records (the resumable SHA-1 state and the CRC after each extent),
     checkpoint_texts() their `.info` texts, marshalled on the device.
+
+    build chooses where the job array, the destination pointers and the record pointers are made.  "host"
+    (the default) fills them with numpy and uploads them, up to 72 bytes per extent.  "device" uploads the
+    compact object table instead -- 16 bytes per extent, 4 per object -- and lets efes_objects_jobs expand it
+    on torch's current stream; the constructor then does not wait for the device, submit() may follow at
+    once, and jobs, _dst, _ckpt_ptrs, copy_offsets and copy_bytes hold the same bytes and values as with
+    "host" (copy_offsets, copy_bytes and jobs_host are read back from the device on first use).
+    from_table() builds the set from a table that already lies in device memory.
     """
 
     _ordered = DeviceBatch._ordered
@@ -273,7 +281,9 @@ class DeviceObjects:
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                  crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                 copy_offsets=None, checkpoints: bool = False):
+                 copy_offsets=None, checkpoints: bool = False, build: str = "host"):
+        if build not in ("host", "device"):
+            raise ValueError(f'DeviceObjects: build={build!r} (build="host" or build="device")')
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
         if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
@@ -290,6 +300,7 @@ class DeviceObjects:
         if states is not None and not sha1:
             raise ValueError("DeviceObjects: states= needs sha1=True")
         self.has_sha1, self.has_crc32 = bool(sha1), bool(crc32)
+        self.build = build
 
         self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
         self.torch = torch
@@ -301,6 +312,16 @@ class DeviceObjects:
         self.first = np.concatenate(([0], np.cumsum(counts)))[:-1] if self.nobjects else np.zeros(0, np.int64)
         self.last = self.first + counts - 1  # job of each object's last extent (first - 1: no extents)
         ext = np.array([e for o in objects for e in o], dtype=np.uint64).reshape(n, 2)
+        if build == "device":  # the compact table goes up; efes_objects_jobs makes the arrays below
+            bounds = np.concatenate(([0], np.cumsum(counts))).astype(np.uint32)
+            offs = None if copy_offsets is None else np.ascontiguousarray(copy_offsets, dtype=np.uint64)
+            assert offs is None or offs.size == self.nobjects
+            self._build_on_device(data_ptr, torch.from_numpy(ext.view(np.int64)).to(device),
+                                  torch.from_numpy(bounds.view(np.int32)).to(device), int((counts > 0).sum()), crcs=crcs,
+                                  fresh=fresh, running=running, states=states, walk=walk, copy_to=copy_to,
+                                  copy_offsets=None if offs is None else torch.from_numpy(offs.view(np.int64)).to(device),
+                                  checkpoints=checkpoints)
+            return
         owner = np.repeat(np.arange(self.nobjects, dtype=np.uint64), counts)
         self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
         assert self.init_crcs.size == self.nobjects
@@ -360,6 +381,115 @@ class DeviceObjects:
                 scratch_bytes = crc32_copy_scratch(n)
         self._scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=device)
         torch.cuda.synchronize(device)
+
+    @classmethod
+    def from_table(cls, data_ptr: int, extents, first, *, crcs: np.ndarray | None = None, fresh: bool = True,
+                   running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
+                   crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
+                   copy_offsets=None, checkpoints: bool = False) -> "DeviceObjects":
+        """The set of an object table that already lies in DEVICE memory: `extents`, a contiguous torch tensor of
+        shape (n, 2) of 64-bit integers, (offset, length) per extent, and `first`, one of shape (nobjects + 1,)
+        of 32-bit integers, object i owning the extents [first[i], first[i + 1]).  The other arguments are the
+        constructor's; copy_offsets, where given, is a device tensor of nobjects 64-bit integers.  The table is
+        never copied to the host while the set is built or submitted (efes_objects_jobs expands it in stream
+        order); first, last, copy_offsets and copy_bytes are fetched when first read, which sha1_hex() does.
+        walk="auto" and "auto_wide" need the number of objects that have extents on the host and raise
+        ValueError: pass "wide", None or an EFES_MODE_* constant."""
+        if checkpoints and not sha1:
+            raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
+        if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
+            raise ValueError('DeviceObjects: copy_to= with sha1=True needs walk="wide" (efes_hash_chain_wide_copy)')
+        if copy_offsets is not None and copy_to is None:
+            raise ValueError("DeviceObjects: copy_offsets= needs copy_to=")
+        if not (sha1 or crc32):
+            raise ValueError("DeviceObjects: sha1 or crc32 (or both)")
+        if (walk is not None or states is not None) and not sha1:
+            raise ValueError("DeviceObjects: walk= and states= need sha1=True")
+        if isinstance(walk, str) and walk in ("auto", "auto_wide"):
+            raise ValueError(f'DeviceObjects.from_table: walk={walk!r} needs the chain count on the host')
+        if extents.dim() != 2 or extents.shape[1] != 2 or extents.element_size() != 8 or not extents.is_contiguous():
+            raise ValueError("DeviceObjects.from_table: extents is a contiguous (n, 2) tensor of 64-bit integers")
+        if first.dim() != 1 or first.numel() < 1 or first.element_size() != 4 or not first.is_contiguous():
+            raise ValueError("DeviceObjects.from_table: first is a contiguous (nobjects + 1,) tensor of 32-bit integers")
+        import torch
+
+        self = cls.__new__(cls)
+        self.has_sha1, self.has_crc32 = bool(sha1), bool(crc32)
+        self.build = "device"
+        self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
+        self.torch = torch
+        self.device = device
+        self.nobjects, self.n = int(first.numel()) - 1, int(extents.shape[0])
+        self._build_on_device(data_ptr, extents, first, None, crcs=crcs, fresh=fresh, running=running, states=states,
+                              walk=walk, copy_to=copy_to, copy_offsets=copy_offsets, checkpoints=checkpoints)
+        return self
+
+    def _build_on_device(self, data_ptr: int, ext, first, nchains, *, crcs, fresh, running, states, walk, copy_to,
+                         copy_offsets, checkpoints) -> None:
+        """The rest of a set whose arrays efes_objects_jobs makes: ext, first (and copy_offsets) are device
+        tensors, kept until the set goes; the states, sums, statuses and records as the host build allocates
+        them; then the call on torch's current stream, with no wait behind it."""
+        torch, device, n, sha1 = self.torch, self.device, self.n, self.has_sha1
+        self._table_ext, self._table_first, self._table_offsets = ext, first, copy_offsets
+        self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
+        assert self.init_crcs.size == self.nobjects
+        self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
+        self.crcs = self._init_crcs_dev.clone() if self.nobjects else torch.zeros(4, dtype=torch.uint8, device=device)
+        self.sums = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=device)
+        self.status = torch.full((max(n, 1),), -99, dtype=torch.int32, device=device)
+        if sha1:
+            self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
+            assert self.init_states.size == self.nobjects
+            self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
+            self.states = self._init_states_dev.clone() if self.nobjects else torch.zeros(104, dtype=torch.uint8, device=device)
+        self.running = bool(running)
+        self.wide, self.walk = self._resolve_walk(walk, nchains)
+        self.jobs = (torch.empty if n else torch.zeros)(max(n, 1) * JOB_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self.has_checkpoints = bool(checkpoints)
+        if checkpoints:
+            if self.walk is None:
+                self.walk = MODE_DEEP
+            self.ckpt = torch.zeros(max(n, 1) * CHECKPOINT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+            self._ckpt_ptrs = (torch.empty if n else torch.zeros)(max(n, 1) * 8, dtype=torch.uint8, device=device)
+        scratch_bytes = hash_chain_scratch(n) if sha1 else crc32_chain_scratch(n)
+        self.copy_to = copy_to
+        if copy_to is not None:
+            self._dst = (torch.empty if n else torch.zeros)(max(n, 1) * 8, dtype=torch.uint8, device=device)
+            self._layout = torch.zeros(self.nobjects + 1, dtype=torch.int64, device=device)
+            if not sha1:
+                scratch_bytes = crc32_copy_scratch(n)
+        # one buffer for the builder and the walks behind it: all of them use it in stream order
+        self._scratch = torch.empty(max(scratch_bytes, objects_jobs_scratch(self.nobjects, n), 16), dtype=torch.uint8, device=device)
+        table = Objects(data=int(data_ptr), extents=ext.data_ptr() or None, first=first.data_ptr(),
+                        sha1=self.states.data_ptr() if sha1 else None, crc32=self.crcs.data_ptr() if self.has_crc32 else None,
+                        sums=self.sums.data_ptr(), status=self.status.data_ptr(),
+                        ckpt=self.ckpt.data_ptr() if checkpoints else None, copy_to=None if copy_to is None else int(copy_to),
+                        copy_offsets=None if copy_offsets is None else copy_offsets.data_ptr(),
+                        nobjects=self.nobjects, nextents=n,
+                        flags=(EFES_OBJECTS_FRESH if fresh else 0) | (EFES_OBJECTS_RUNNING if running else 0), copy_align=COPY_ALIGN)
+        out = ObjectsOut(jobs=self.jobs.data_ptr(), dst=self._dst.data_ptr() if copy_to is not None else None,
+                         ckpt=self._ckpt_ptrs.data_ptr() if checkpoints else None,
+                         layout=self._layout.data_ptr() if copy_to is not None else None)
+        self._ordered(lambda stream: self.ctx.objects_jobs(table, out, self._scratch.data_ptr(), self._scratch.numel(), stream))
+
+    _FETCHED = ("first", "last", "copy_offsets", "copy_bytes", "jobs_host")
+
+    def __getattr__(self, name):
+        """What a set built on the device leaves there until it is read: the object boundaries of from_table(),
+        the gather layout, the job records."""
+        d = self.__dict__
+        if name in DeviceObjects._FETCHED and "_table_first" in d:
+            if name in ("first", "last"):
+                f = d["_table_first"].cpu().numpy().view(np.uint32).astype(np.int64)
+                self.first, self.last = f[:-1], f[1:] - 1
+            elif name == "jobs_host":
+                self.jobs_host = self.jobs.cpu().numpy()[: self.n * JOB_DTYPE.itemsize].view(JOB_DTYPE).copy()
+            elif d.get("copy_to") is not None:
+                lay = d["_layout"].cpu().numpy().view(np.uint64)
+                self.copy_offsets, self.copy_bytes = lay[:-1].copy(), int(lay[-1])
+            if name in d:
+                return d[name]
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def reset(self) -> None:
         """Restore the initial states (async, on torch's current stream)."""

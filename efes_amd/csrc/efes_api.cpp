@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "efes_internal.hpp"
+#include "efes_objects_rules.hpp"
 
 using efes::Tables;
 
@@ -488,6 +489,23 @@ int efes_hash_chain_auto_mode_wide(const efes_ctx* ctx, uint32_t nchains) {
   const uint64_t simds = 4ull * (ctx ? (uint64_t)ctx->cus : 256ull);
   if ((uint64_t)nchains >= kChainWideFrom * simds) return EFES_MODE_WIDE;
   return efes_hash_chain_auto_mode(ctx, nchains);
+}
+
+size_t efes_objects_jobs_scratch(uint32_t nobjects, uint32_t nextents) {
+  return efes::objects_jobs_scratch_bytes(nobjects, nextents);
+}
+
+int efes_objects_jobs(efes_ctx* ctx, const efes_objects* in, const efes_objects_out* out, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::objects_check(in, out);
+  if (rc != EFES_OK) return rc;
+  if (in->nextents == 0 && !out->layout) return EFES_OK;  // nothing to launch
+  if (in->nextents && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+                       scratch_bytes < efes::objects_jobs_scratch_bytes(in->nobjects, in->nextents)))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_objects_jobs(*in, *out, scratch, pick(ctx, stream)));
 }
 
 int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, uint32_t n, char* text, void* stream) {

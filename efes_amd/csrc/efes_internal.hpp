@@ -185,6 +185,11 @@ hipError_t launch_hash_chain_wide(const efes_job* jobs, uint32_t njobs, efes_che
 hipError_t launch_hash_chain_wide_copy(const efes_job* jobs, void* const* dsts, uint32_t njobs,
                                        efes_checkpoint* const* ckpt, void* scratch, const Tables* tabs, int cus,
                                        hipStream_t s);
+// Object tables (efes_objects_jobs, efes_objects.hip): two-level 64-bit scans of the extent lengths and of the
+// rounded object sizes over the scratch, then one pass that writes the jobs, dst[] and ckpt[]; every grid is
+// sized from an element count.  The arguments are checked by the caller (objects_check, efes_objects_rules.hpp).
+size_t objects_jobs_scratch_bytes(uint32_t nobjects, uint32_t nextents);
+hipError_t launch_objects_jobs(const efes_objects& in, const efes_objects_out& out, void* scratch, hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 

@@ -23,9 +23,9 @@ import threading
 
 import numpy as np
 
-from ._lib import MODE_AUTO, EfesError, PairStats, Plan, QueueStats, Sha1State, check, lib
+from ._lib import MODE_AUTO, EfesError, Objects, ObjectsOut, PairStats, Plan, QueueStats, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -79,6 +79,18 @@ def hash_chain_auto_mode_wide(nchains: int, ctx: "Context | None" = None) -> int
     MODE_WIDE from the measured chain count upwards (that result goes to hash_chain_wide()), else what
     hash_chain_auto_mode() gives (that goes to hash_chain_mode()).  Host-only."""
     return int(lib().efes_hash_chain_auto_mode_wide(ctx.handle if ctx else None, nchains))
+
+
+def objects_jobs_scratch(nobjects: int, nextents: int) -> int:
+    """efes_objects_jobs_scratch: device bytes efes_objects_jobs needs for a table of nobjects objects and
+    nextents extents (0 where either exceeds EFES_OBJECTS_MAX)."""
+    return int(lib().efes_objects_jobs_scratch(nobjects, nextents))
+
+
+def objects_jobs_host(table: Objects, out: ObjectsOut) -> None:
+    """efes_objects_jobs_host: objects_jobs() on the host -- extents, first, copy_offsets and every array of
+    `out` are host addresses; the base addresses in `table` are only added to.  Needs no GPU."""
+    check(lib().efes_objects_jobs_host(ctypes.byref(table), ctypes.byref(out)), "efes_objects_jobs_host")
 
 
 class Context:
@@ -179,6 +191,15 @@ class Context:
         hashed, not copied).  ckpt_ptr, the scratch and everything written as for hash_chain_wide()."""
         check(lib().efes_hash_chain_wide_copy(self.handle, jobs_ptr, dst_ptr, ckpt_ptr, njobs, scratch_ptr, scratch_bytes,
                                               stream), "efes_hash_chain_wide_copy")
+
+    def objects_jobs(self, table: Objects, out: ObjectsOut, scratch_ptr: int | None, scratch_bytes: int,
+                     stream: int | None = None) -> None:
+        """efes_objects_jobs: the object table `table` (extents and object boundaries in device memory, the base
+        addresses of data, states, sums, statuses, records and the gather destination) expanded on the device
+        into the job array, dst[] and ckpt[] of `out`, and the gather layout; asynchronous on `stream`, so a
+        chain call queued behind it on the same stream needs no synchronisation in between."""
+        check(lib().efes_objects_jobs(self.handle, ctypes.byref(table), ctypes.byref(out), scratch_ptr, scratch_bytes,
+                                      stream), "efes_objects_jobs")
 
     def checkpoints_marshal_text(self, ckpt_ptr: int, n: int, text_ptr: int, stream: int | None = None) -> None:
         """efes_checkpoints_marshal_text: the `.info` texts of n contiguous device records at ckpt_ptr,

@@ -793,6 +793,110 @@ int efes_hash_chain_wide_copy(efes_ctx* ctx, const efes_job* jobs_device, void* 
                               efes_checkpoint* const* ckpt_device, uint32_t njobs, void* scratch_device,
                               size_t scratch_bytes, void* stream);
 
+/* Object tables: the arrays the chain calls take, built ON THE DEVICE.  Every chain call above takes a device
+ * array of 56-byte jobs, one per extent; the gather calls add dst[], the checkpoint calls ckpt[].  A job is
+ * six pointers and a flag word, and all of them follow from the extent's (offset, length), the object it
+ * belongs to and its index, given seven base addresses.  efes_objects_jobs expands an OBJECT TABLE -- the
+ * extents and the object boundaries, 16 bytes per extent and 4 per object, in device memory -- into the job
+ * array, the destination pointers and the record pointers, in stream order, directly in front of any chain
+ * call: a caller whose extents live in a device-side pool needs no round trip through the host, and a host
+ * caller uploads 16 instead of up to 72 bytes per extent.  The gather layout falls out of the same scans.
+ *
+ * efes_objects and efes_objects_out are HOST structs; the pointers in them are device addresses.  Object i
+ * owns the extents [first[i], first[i + 1]); an object without extents takes no job.  For extent j let
+ * i = owner(j) be the largest i in [0, nobjects) with first[i] <= j (0 if there is none).  Written:
+ *   - jobs[j]: data = data + extents[j].offset, length = extents[j].length, sha1 = sha1 ? sha1 + i : NULL,
+ *     crc32 = crc32 ? crc32 + i : NULL, sum = sums + 24 j, status = status ? status + j : NULL, _reserved = 0;
+ *     flags = EFES_JOB_INIT (EFES_OBJECTS_FRESH) or 0 where j == first[i], EFES_JOB_CHAIN on every other
+ *     extent, plus EFES_JOB_FINALIZE where j + 1 == first[i + 1], or on every extent with EFES_OBJECTS_RUNNING;
+ *   - out->ckpt[j] = in->ckpt + j (112-byte records), when in->ckpt != NULL;
+ *   - out->dst[j] = copy_to + L[i] + within(j), when copy_to != NULL: within(j) is the sum of the lengths of
+ *     the object's extents before j and L the layout -- copy_offsets[i] where given, else the exclusive prefix
+ *     sum, over the objects before i, of their sizes rounded up to copy_align (a power of two <= 2^20; 0 =
+ *     EFES_OBJECTS_COPY_ALIGN): the objects back to back in their order, each start aligned;
+ *   - out->layout (may be NULL; may be asked for without copy_to): layout[i] = L[i] for i < nobjects, and
+ *     layout[nobjects] = the room the layout needs behind copy_to: L[nobjects - 1] + size[nobjects - 1] in the
+ *     default layout, max(copy_offsets[i] + size[i]) with explicit offsets, 0 for no objects.
+ * All arithmetic is modulo 2^64.  Nothing outside the named output arrays (and the scratch) is written.
+ * SAFETY PROPERTY: every pointer emitted is formed from an index inside [0, nobjects) or [0, nextents),
+ * whatever first[] holds.  The fill runs one thread per output element and clamps the owner: the binary
+ * search reads first[0, nobjects) only and returns an index of that range, a boundary is read at
+ * first[0, nobjects] only and clamped to [0, nextents] before it indexes the scanned lengths.  A table that
+ * is not non-decreasing, or whose first[0] != 0 or first[nobjects] != nextents, therefore gives unspecified
+ * but in-range jobs (with nobjects == 0 and nextents > 0 the one index there is, 0, is used: such a table
+ * has no state to point at and its jobs must not be run).
+ * Errors, checked first and without the device: EFES_ERR_ARG for a NULL ctx, in or out and for nobjects or
+ * nextents > EFES_OBJECTS_MAX; with nextents > 0 also for NULL extents, first, sums or out->jobs, for sha1 and
+ * crc32 both NULL, copy_to without out->dst, in->ckpt without out->ckpt, copy_offsets without copy_to, unknown
+ * flag bits, a copy_align that is no power of two or exceeds 2^20, and a scratch that is NULL, not 16-byte
+ * aligned or smaller than efes_objects_jobs_scratch(nobjects, nextents) (0 for counts the call refuses).
+ * nextents == 0 launches nothing for jobs and needs no scratch; it still writes layout when asked (with
+ * nobjects == 0 the single word layout[0] = 0).
+ * Asynchronous on `stream` (NULL = the context stream), no host read-back, allocation or wait; the scratch is
+ * used in stream order, as the chain calls use theirs.  The outputs are visible to later work in stream
+ * order: a chain call queued behind it on the same stream needs no host synchronisation in between.
+ * Two-level 64-bit scans of the lengths and of the rounded sizes, a 64-bit maximum by vector atomics, and
+ * one fill pass that looks the owner up once per extent and stores every output as contiguous 64-bit words
+ * (DESIGN.md §4 "Object tables"); every grid is sized from an element count, none from the CU count.
+ *
+ * efes_objects_jobs_host is the same function with extents, first, copy_offsets and all of out in HOST
+ * memory, and no context, scratch or stream: the base addresses are only added to, never dereferenced.  For
+ * a caller whose table is on the host but who does not want to restate the flag rules (the Go binding), and
+ * for checking the contract on a machine without a GPU.  The same argument errors, EFES_ERR_NOMEM if its own
+ * working arrays cannot be had.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/objects_jobs/bench.json; DESIGN.md §4 "Object tables" has the table; fused sets
+ * with a record per extent and the default gather layout, so all three arrays are made; "host build" = the numpy
+ * fill of the three arrays from packed extent and count arrays, their upload and a synchronise, "device build" =
+ * the upload of the table, this call and a synchronise, both wall-clock medians):
+ *   - on every shape measured: the device build, at 0.03 to 0.08 of the host build's time, its median below the
+ *     host build's minimum on all five -- 0.16 ms against 1.9 (32 768 objects x 4 extents), 0.32 against 4.2
+ *     (65 536 x 4), 0.24 against 3.8 (4096 x 64), 0.33 against 5.4 (65 536 objects of 1-8 extents) and 0.86 ms
+ *     against 31.6 (262 144 x 4, 1 048 576 extents);
+ *   - the call alone takes 25, 29, 29, 33 and 55 us of device time on these shapes: 0.8, 1.8, 0.4, 0.2 and 3.9 % of
+ *     the efes_hash_chain_wide call behind it (3.1, 1.6, 6.6, 15.9 and 1.4 ms).  The host build takes 0.3 to 2.6
+ *     times that walk's time, and 22 times at 262 144 x 4: 31.6 ms of host work in front of a 1.4 ms walk;
+ *   - the call is NOT bandwidth-bound at these sizes, as it was expected to be: 0.5 to 1.7 TB/s read plus written,
+ *     6 to 22 % of the 8 TB/s HBM peak.  Its five or six launches of a few microseconds each are what it costs;
+ *   - neither build is what a Python caller pays for first: flattening Python lists of extents into the packed
+ *     arrays takes 34 to 460 ms on these shapes, more than either build.  A caller with many objects keeps its
+ *     extents packed, or on the device (DeviceObjects.from_table). */
+typedef struct efes_extent {
+    uint64_t offset; /* extent j lies at data + offset */
+    uint64_t length;
+} efes_extent; /* 16 bytes */
+
+#define EFES_OBJECTS_FRESH 0x1u   /* every object's first extent carries EFES_JOB_INIT */
+#define EFES_OBJECTS_RUNNING 0x2u /* every extent carries EFES_JOB_FINALIZE; else each object's last one */
+#define EFES_OBJECTS_MAX EFES_HASH_CHAIN_MAX_JOBS /* nobjects and nextents, each */
+#define EFES_OBJECTS_COPY_ALIGN 256u
+
+typedef struct efes_objects {      /* a HOST struct; the pointers in it are device addresses */
+    const void* data;              /* extent j lies at data + extents[j].offset */
+    const efes_extent* extents;    /* nextents */
+    const uint32_t* first;         /* nobjects + 1: object i owns extents [first[i], first[i+1]) */
+    efes_sha1_state* sha1;         /* nobjects states, or NULL: no SHA-1 */
+    efes_crc32_state* crc32;       /* nobjects states, or NULL: no CRC */
+    uint8_t* sums;                 /* 24 * nextents */
+    int32_t* status;               /* nextents, or NULL */
+    efes_checkpoint* ckpt;         /* nextents records, or NULL: no record pointers */
+    void* copy_to;                 /* or NULL: no destination pointers */
+    const uint64_t* copy_offsets;  /* nobjects, or NULL: the default layout */
+    uint32_t nobjects, nextents, flags, copy_align; /* copy_align 0 = EFES_OBJECTS_COPY_ALIGN */
+} efes_objects; /* 96 bytes: ten pointers, four 32-bit words */
+
+typedef struct efes_objects_out { /* a HOST struct of device addresses */
+    efes_job* jobs;               /* nextents */
+    void** dst;                   /* nextents; needed exactly when copy_to != NULL */
+    efes_checkpoint** ckpt;       /* nextents; needed exactly when in->ckpt != NULL */
+    uint64_t* layout;             /* nobjects + 1, or NULL */
+} efes_objects_out; /* 32 bytes */
+
+size_t efes_objects_jobs_scratch(uint32_t nobjects, uint32_t nextents);
+int efes_objects_jobs(efes_ctx* ctx, const efes_objects* in, const efes_objects_out* out, void* scratch_device,
+                      size_t scratch_bytes, void* stream);
+int efes_objects_jobs_host(const efes_objects* in, const efes_objects_out* out);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */
