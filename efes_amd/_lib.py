@@ -119,6 +119,22 @@ OBJECTS_SCAN_BLOCK = 1024  # kObjectsBlock of efes_objects.hip: lanes of one sca
 EXTENT_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8")])
 assert ctypes.sizeof(Extent) == 16 == EXTENT_DTYPE.itemsize and ctypes.sizeof(Objects) == 96 and ctypes.sizeof(ObjectsOut) == 32
 
+class ObjectResult(ctypes.Structure):
+    """efes_object_result: one object's digest, status and verdict (efes_objects_results)."""
+    _fields_ = [("sum", ctypes.c_uint8 * 24), ("status", ctypes.c_int32), ("verdict", ctypes.c_uint32)]
+
+
+class Results(ctypes.Structure):
+    """efes_results: what efes_objects_results compares with and where it writes; a host struct of device addresses
+    (host ones for efes_objects_results_host)."""
+    _fields_ = [("expected", ctypes.c_void_p), ("compare", ctypes.c_uint32), ("_reserved", ctypes.c_uint32),
+                ("results", ctypes.c_void_p), ("bad", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+EFES_VERDICT_OK, EFES_VERDICT_MISMATCH, EFES_VERDICT_FAILED, EFES_VERDICT_EMPTY = 0, 1, 2, 3
+OBJECT_RESULT_DTYPE = np.dtype([("sum", "u1", (24,)), ("status", "<i4"), ("verdict", "<u4")])
+assert ctypes.sizeof(ObjectResult) == 32 == OBJECT_RESULT_DTYPE.itemsize and ctypes.sizeof(Results) == 40
+
 assert ctypes.sizeof(Sha1State) == 104 and ctypes.sizeof(Job) == 56 and ctypes.sizeof(QueueStats) == 32
 assert ctypes.sizeof(PairStats) == 32
 
@@ -221,6 +237,9 @@ SIGNATURES = {
     "efes_objects_jobs_scratch": (_S, [_U32, _U32]),
     "efes_objects_jobs": (_I, [_VP, _P(Objects), _P(ObjectsOut), _VP, _S, _VP]),
     "efes_objects_jobs_host": (_I, [_P(Objects), _P(ObjectsOut)]),
+    "efes_objects_results_scratch": (_S, [_U32, _U32]),
+    "efes_objects_results": (_I, [_VP, _P(Objects), _P(Results), _VP, _S, _VP]),
+    "efes_objects_results_host": (_I, [_P(Objects), _P(Results)]),
     "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),

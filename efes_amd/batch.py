@@ -9,9 +9,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
-                   MODE_FED4E, MODE_GROUP, MODE_WIDE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Objects, ObjectsOut, Plan, PlanPart)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_scratch
+from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_HASH_CRC32, EFES_HASH_SHA1, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
+                   MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Objects, ObjectsOut, Plan, PlanPart, Results)
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_scratch, objects_results_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -274,6 +274,10 @@ class DeviceObjects:
     once, and jobs, _dst, _ckpt_ptrs, copy_offsets and copy_bytes hold the same bytes and values as with
     "host" (copy_offsets, copy_bytes and jobs_host are read back from the device on first use).
     from_table() builds the set from a table that already lies in device memory.
+
+    verify(expected) and results() sort the per-extent sums and statuses out per object ON THE DEVICE
+    (efes_objects_results): verdicts against expected digests, the ascending list of the objects that are not in
+    order and four counters, of which verify() copies only the counters and the list to the host.
     """
 
     _ordered = DeviceBatch._ordered
@@ -599,6 +603,81 @@ class DeviceObjects:
         self._ordered(lambda stream: self.ctx.checkpoints_marshal_text(self.ckpt.data_ptr(), self.n, text.data_ptr(), stream))
         rows = text.cpu().numpy()[: self.n * CHECKPOINT_TEXT_BYTES].reshape(self.n, CHECKPOINT_TEXT_BYTES)
         return [(bytes(r[:200]), bytes(r[200:])) for r in rows]
+
+
+    # ---- results sorted out on the device (efes_objects_results)
+    def _results_args(self, expected, compare):
+        """(expected, compare) of results() and verify(), checked from the arguments alone: no device is touched."""
+        if compare is None:  # the digests the set keeps
+            compare = (EFES_HASH_SHA1 if self.has_sha1 else 0) | (EFES_HASH_CRC32 if self.has_crc32 else 0)
+        if isinstance(compare, bool) or not isinstance(compare, (int, np.integer)) or compare < 0 or compare & ~(EFES_HASH_SHA1 | EFES_HASH_CRC32):
+            raise ValueError(f"DeviceObjects: compare={compare!r} (EFES_HASH_SHA1 | EFES_HASH_CRC32, or 0)")
+        if expected is not None:
+            if not hasattr(expected, "data_ptr"):
+                expected = np.asarray(expected)
+            if tuple(expected.shape) != (self.nobjects, 24) or str(expected.dtype) not in ("uint8", "torch.uint8"):
+                raise ValueError(f"DeviceObjects: expected is a ({self.nobjects}, 24) uint8 array, laid out like the sums "
+                                 f"(got {tuple(expected.shape)} {expected.dtype})")
+            if hasattr(expected, "data_ptr") and not expected.is_contiguous():
+                raise ValueError("DeviceObjects: expected is a contiguous tensor")
+        return expected, int(compare)
+
+    def _results_call(self, expected, compare, records: bool):
+        """efes_objects_results on torch's current stream, over buffers the set allocates once and keeps; the record
+        array (a device tensor) when asked for.  A host-built set uploads its nobjects + 1 boundaries the first
+        time; a set built from a device table uses that table's and copies nothing to the host."""
+        torch, device, m = self.torch, self.device, self.nobjects
+        d = self.__dict__
+        if "_res_first" not in d:
+            first = d.get("_table_first")
+            if first is None:
+                first = torch.from_numpy(np.concatenate((self.first, [self.n])).astype(np.uint32).view(np.int32)).to(device)
+            self._res_counts = torch.zeros(4, dtype=torch.int32, device=device)
+            self._res_bad = torch.empty(max(m, 1), dtype=torch.int32, device=device)
+            self._res_scratch = torch.empty(max(objects_results_scratch(m, self.n), 16), dtype=torch.uint8, device=device)
+            self._res_first = first
+        if expected is not None and not hasattr(expected, "data_ptr"):
+            expected = torch.from_numpy(np.ascontiguousarray(expected)).to(device)
+        elif expected is not None and str(expected.device) != str(torch.device(device)):
+            expected = expected.to(device)
+        if records and "_res_records" not in d:  # kept like the other buffers: it outlives every launch that writes it
+            self._res_records = torch.empty(max(m, 1) * OBJECT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        rec = self._res_records if records else None
+        table = Objects(first=self._res_first.data_ptr(), sums=self.sums.data_ptr(), status=self.status.data_ptr(),
+                        nobjects=m, nextents=self.n)
+        req = Results(expected=(expected.data_ptr() or None) if expected is not None else None, compare=compare,
+                      results=rec.data_ptr() if records else None, bad=self._res_bad.data_ptr(), counts=self._res_counts.data_ptr())
+        self._ordered(lambda stream: self.ctx.objects_results(table, req, self._res_scratch.data_ptr(), self._res_scratch.numel(), stream))
+        self._res_expected = expected  # alive until the next call
+        return rec
+
+    def _results_fetch(self):
+        """(counts, bad): the 16 bytes of the counters, then as many words of the list as they say."""
+        counts = self._res_counts.cpu().numpy().view(np.uint32).copy()
+        nbad = int(counts[1]) + int(counts[2])
+        bad = self._res_bad[:nbad].cpu().numpy().view(np.uint32).copy() if nbad else np.zeros(0, np.uint32)
+        return counts, bad
+
+    def verify(self, expected, compare=None):
+        """(counts, bad): counts[v] = the objects with verdict v (EFES_VERDICT_OK, MISMATCH, FAILED, EMPTY), bad =
+        the ascending indices of the objects whose verdict is MISMATCH or FAILED, sorted out on the device by
+        efes_objects_results from the sums and statuses the last run left.  expected is a (nobjects, 24) uint8
+        array laid out like a sum (the SHA-1 Sum, then the CRC big-endian), host numpy or a device tensor, or
+        None: nothing is compared and only failures are bad.  compare = EFES_HASH_SHA1 | EFES_HASH_CRC32 selects
+        the bytes compared; the default is the digests the set keeps.  On torch's current stream, behind the run;
+        only the 16 bytes of counts and then bad[:counts[1] + counts[2]] are copied to the host."""
+        expected, compare = self._results_args(expected, compare)
+        self._results_call(expected, compare, records=False)
+        return self._results_fetch()
+
+    def results(self, expected=None, compare=None):
+        """(records, counts, bad): records is the per-object array of OBJECT_RESULT_DTYPE -- the sum of the object's
+        last extent (zeros where it failed or the object has no extents), the status of its first member that is
+        not EFES_OK, the verdict --, counts and bad as verify() gives them."""
+        expected, compare = self._results_args(expected, compare)
+        rec = self._results_call(expected, compare, records=True)
+        counts, bad = self._results_fetch()
+        return rec.cpu().numpy()[: self.nobjects * OBJECT_RESULT_DTYPE.itemsize].view(OBJECT_RESULT_DTYPE).copy(), counts, bad
 
 
 class PinnedHostBuffer:

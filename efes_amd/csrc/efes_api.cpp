@@ -508,6 +508,22 @@ int efes_objects_jobs(efes_ctx* ctx, const efes_objects* in, const efes_objects_
   return hip_err(efes::launch_objects_jobs(*in, *out, scratch, pick(ctx, stream)));
 }
 
+size_t efes_objects_results_scratch(uint32_t nobjects, uint32_t nextents) {
+  return efes::objects_results_scratch_bytes(nobjects, nextents);
+}
+
+int efes_objects_results(efes_ctx* ctx, const efes_objects* in, const efes_results* req, void* scratch,
+                         size_t scratch_bytes, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::results_check(in, req);
+  if (rc != EFES_OK) return rc;
+  if (in->nobjects && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+                       scratch_bytes < efes::objects_results_scratch_bytes(in->nobjects, in->nextents)))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_objects_results(*in, *req, scratch, pick(ctx, stream)));
+}
+
 int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, uint32_t n, char* text, void* stream) {
   if (!ctx || n > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
   if (n == 0) return EFES_OK;

@@ -190,6 +190,11 @@ hipError_t launch_hash_chain_wide_copy(const efes_job* jobs, void* const* dsts, 
 // sized from an element count.  The arguments are checked by the caller (objects_check, efes_objects_rules.hpp).
 size_t objects_jobs_scratch_bytes(uint32_t nobjects, uint32_t nextents);
 hipError_t launch_objects_jobs(const efes_objects& in, const efes_objects_out& out, void* scratch, hipStream_t s);
+// Object results (efes_objects_results, efes_objects_results.hip): the first failing member of every object by one
+// lane per extent and an atomic minimum, one pass per object for the result records, a two-level scan of the bad
+// flags for the ascending list.  The arguments are checked by the caller (results_check, efes_objects_rules.hpp).
+size_t objects_results_scratch_bytes(uint32_t nobjects, uint32_t nextents);
+hipError_t launch_objects_results(const efes_objects& in, const efes_results& req, void* scratch, hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 

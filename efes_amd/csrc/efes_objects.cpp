@@ -1,6 +1,9 @@
 // efes_objects.cpp -- efes_objects_jobs_host: the object table expanded into job records on the HOST
 // (efes_hash.h "Object tables").  The same rules as the device kernels (efes_objects_rules.hpp), one plain
-// loop each; the base addresses in the table are only added to, never dereferenced.
+// loop each; the base addresses in the table are only added to, never dereferenced.  Behind it
+// efes_objects_results_host, the per-object results of such a table ("Object results"), likewise.
+#include <string.h>
+
 #include <vector>
 
 #include "efes_objects_rules.hpp"
@@ -65,5 +68,36 @@ extern "C" int efes_objects_jobs_host(const efes_objects* in, const efes_objects
       out->dst[j] = (void*)(copy_to + here + (E[j] - E[efes::objects_bound(in->first, i, n)]));
     }
   }
+  return EFES_OK;
+}
+
+// efes_objects_results_host: the per-object results (efes_hash.h "Object results") on the HOST.  The rules are
+// results_object's, as on the device; the first failing member of every object is found as there, through the
+// owner of each member that failed, so a table that breaks the rules gives the same in-range answers.
+extern "C" int efes_objects_results_host(const efes_objects* in, const efes_results* req) {
+  const int rc = efes::results_check(in, req);
+  if (rc != EFES_OK) return rc;
+  const uint32_t n = in->nextents, m = in->nobjects;
+  std::vector<uint32_t> fail;
+  try {
+    fail.assign(m, efes::kResultsNone);
+  } catch (...) {
+    return EFES_ERR_NOMEM;
+  }
+  if (m)
+    for (uint32_t j = 0; j < n; ++j) {
+      if (in->status[j] == EFES_OK) continue;
+      uint32_t& f = fail[efes::objects_owner(in->first, m, j)];
+      if (j < f) f = j;
+    }
+  uint32_t counts[4] = {0, 0, 0, 0}, nbad = 0;
+  for (uint32_t i = 0; i < m; ++i) {
+    uint32_t w[efes::kResultWords];
+    efes::results_object(in->first, n, in->status, in->sums, req->expected, req->compare, i, fail[i], w);
+    if (req->results) memcpy(req->results + i, w, sizeof w);
+    ++counts[w[7]];
+    if (req->bad && efes::results_is_bad(w[7])) req->bad[nbad++] = i;
+  }
+  memcpy(req->counts, counts, sizeof counts);
   return EFES_OK;
 }

@@ -23,9 +23,9 @@ import threading
 
 import numpy as np
 
-from ._lib import MODE_AUTO, EfesError, Objects, ObjectsOut, PairStats, Plan, QueueStats, Sha1State, check, lib
+from ._lib import MODE_AUTO, EfesError, Objects, ObjectsOut, PairStats, Plan, QueueStats, Results, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -91,6 +91,18 @@ def objects_jobs_host(table: Objects, out: ObjectsOut) -> None:
     """efes_objects_jobs_host: objects_jobs() on the host -- extents, first, copy_offsets and every array of
     `out` are host addresses; the base addresses in `table` are only added to.  Needs no GPU."""
     check(lib().efes_objects_jobs_host(ctypes.byref(table), ctypes.byref(out)), "efes_objects_jobs_host")
+
+
+def objects_results_scratch(nobjects: int, nextents: int) -> int:
+    """efes_objects_results_scratch: device bytes efes_objects_results needs for a table of nobjects objects and
+    nextents extents (0 where either exceeds EFES_OBJECTS_MAX, never 0 otherwise)."""
+    return int(lib().efes_objects_results_scratch(nobjects, nextents))
+
+
+def objects_results_host(table: Objects, req: Results) -> None:
+    """efes_objects_results_host: objects_results() on the host -- first, sums and status of `table` and every
+    array of `req` are host addresses.  Needs no GPU."""
+    check(lib().efes_objects_results_host(ctypes.byref(table), ctypes.byref(req)), "efes_objects_results_host")
 
 
 class Context:
@@ -200,6 +212,16 @@ class Context:
         chain call queued behind it on the same stream needs no synchronisation in between."""
         check(lib().efes_objects_jobs(self.handle, ctypes.byref(table), ctypes.byref(out), scratch_ptr, scratch_bytes,
                                       stream), "efes_objects_jobs")
+
+    def objects_results(self, table: Objects, req: Results, scratch_ptr: int | None, scratch_bytes: int,
+                        stream: int | None = None) -> None:
+        """efes_objects_results: from the object table `table` (the one objects_jobs() was given) and the sums and
+        statuses a chain call left behind it, one 32-byte result per object (digest, status, verdict against
+        req.expected under req.compare), the ascending list of the objects whose verdict is MISMATCH or FAILED,
+        and the four verdict counters, all in device memory; asynchronous on `stream`, so queued behind the chain
+        call on the same stream it needs no synchronisation in between."""
+        check(lib().efes_objects_results(self.handle, ctypes.byref(table), ctypes.byref(req), scratch_ptr, scratch_bytes,
+                                         stream), "efes_objects_results")
 
     def checkpoints_marshal_text(self, ckpt_ptr: int, n: int, text_ptr: int, stream: int | None = None) -> None:
         """efes_checkpoints_marshal_text: the `.info` texts of n contiguous device records at ckpt_ptr,

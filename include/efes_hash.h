@@ -897,6 +897,107 @@ int efes_objects_jobs(efes_ctx* ctx, const efes_objects* in, const efes_objects_
                       size_t scratch_bytes, void* stream);
 int efes_objects_jobs_host(const efes_objects* in, const efes_objects_out* out);
 
+/* Object results: what a chain call left for an object table, sorted out ON THE DEVICE.  The walks leave a
+ * 24-byte sum and a status per EXTENT; every caller asks per OBJECT, and what it asks is a check: the objects
+ * re-checked after a copy or drain, the gather before a write-out, the uploader that compares its SHA-1 with the
+ * efes-file-sha1 the server returned and fails on a mismatch (write.go:112-114).  efes_objects_results takes the
+ * table efes_objects_jobs was given and the sums and statuses behind it, and writes one 32-byte result per object
+ * (digest, status, verdict against an expected digest), the ascending list of the objects that are not in order,
+ * and four counters: a caller that only wants to know whether everything matched reads back 16 bytes.
+ *
+ * `in` is the very table efes_objects_jobs was given; only first, sums, status, nobjects and nextents of it are
+ * read, never the extents or the data.  Object i owns the extents [first[i], first[i + 1]):
+ *   - an object with no extents gets 24 zero bytes, status EFES_OK and verdict EFES_VERDICT_EMPTY; its expected
+ *     entry is never read;
+ *   - otherwise let l = first[i + 1] - 1.  status is the status of the lowest-indexed member whose status is not
+ *     EFES_OK, else EFES_OK.  sum is sums[24 l, 24 l + 24) when status[l] == EFES_OK, otherwise 24 zero bytes: a
+ *     member that failed wrote no sum, so stale bytes are never reported;
+ *   - verdict: FAILED when the object's status is not EFES_OK (expected is not read for it); otherwise MISMATCH
+ *     when expected != NULL and a byte range selected by `compare` differs (EFES_HASH_SHA1: bytes 0..19,
+ *     EFES_HASH_CRC32: bytes 20..23; compare == 0 compares nothing); otherwise OK;
+ *   - bad[k] is the index of the k-th object, in ascending order, whose verdict is MISMATCH or FAILED: exactly
+ *     counts[1] + counts[2] words are written and nothing behind them; the list is sorted, not "some order";
+ *   - counts[v] = the objects with verdict v; always written, all four words, all zeros for nobjects == 0.
+ * Nothing outside the named outputs (and the scratch) is written; results and bad may each be NULL.
+ * The caller's contract, documented and not checked: the sums and statuses are those a chain call left for
+ * `in`'s job array, each object's last extent carried EFES_JOB_FINALIZE (as efes_objects_jobs tables do), and the
+ * outputs overlap nothing else.
+ * SAFETY PROPERTY, as for efes_objects_jobs: every index that forms an address is clamped into [0, nobjects) or
+ * [0, nextents), whatever first[] holds (the same owner search and boundary clamp).  A table that is not
+ * non-decreasing gives unspecified but in-range results.
+ * Errors, checked first and without the device: EFES_ERR_ARG for a NULL ctx, in or req, a NULL counts, nobjects or
+ * nextents > EFES_OBJECTS_MAX, unknown compare bits or a nonzero _reserved; with nobjects > 0 a NULL first; with
+ * nextents > 0 a NULL sums or status (a table built without a status array is refused); sums or expected not
+ * 4-byte aligned; results not 8-byte aligned, bad or counts not 4-byte aligned; and, with nobjects > 0, a scratch
+ * that is NULL, not 16-byte aligned or smaller than efes_objects_results_scratch(nobjects, nextents) (0 for counts
+ * the call refuses, never 0 otherwise).  nobjects == 0 needs no scratch.  A refused call writes nothing.
+ * Asynchronous on `stream` (NULL = the context stream), no host read-back, allocation or wait: queued behind a
+ * chain call on the same stream it needs no synchronisation in between.
+ * No lane loops over an object's members (one object may own all 2^20 extents): the first failing member is found
+ * with one lane per extent -- the owner by the builder's binary search, only for a member that failed, then a
+ * 32-bit atomic minimum of the member's index into a per-object word of the scratch, which the call sets to
+ * "none" itself, in stream order; the per-object pass reads that word, the status it names, the last member's
+ * status where that is another one, and at most one sum, and compares it as six 32-bit words under the two
+ * masks; the bad list is a two-level exclusive scan of the bad flags, each lane storing its own index at its
+ * rank; the counters are the sums of per-workgroup counts, so counts[1] + counts[2] is the scan's total.  Every
+ * grid is sized from an element count (DESIGN.md §4 "Object results").
+ *
+ * efes_objects_results_host is the same function with every array in HOST memory and no context, scratch or
+ * stream: for a caller that already has the sums on the host, and for checking the rules on a machine without a
+ * GPU.  The same argument errors, EFES_ERR_NOMEM if its own working array cannot be had.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/objects_results/bench.json; DESIGN.md §4 "Object results" has the table; sets
+ * of the builder's five shapes with random sums, every status EFES_OK and none or 1 % of the expected digests spoiled;
+ * "verify" = DeviceObjects.verify(): this call with `expected` on the device, a synchronise, the 16 bytes of counts
+ * and then the bad list to the host; "host path" = what the library offered before: the 24 + 4 bytes per extent
+ * copied to the host and a VECTORISED numpy pick of the last extents and compare; wall-clock, verify's median
+ * against the host path's minimum):
+ *   - on the builder's five shapes: this call, in every case measured.  With no bad object verify takes 0.049 ms
+ *     against 0.95 (32 768 objects x 4 extents), 0.051 against 1.76 (65 536 x 4), 0.048 against 0.43 (4096 x 64), 0.047
+ *     against 2.31 (65 536 objects of 1-8 extents) and 0.23 ms against 7.66 (262 144 x 4, 1 048 576 extents): 0.02 to
+ *     0.11 of the host path's time; with 1 % of the digests differing 0.063, 0.071, 0.063, 0.062 and 0.22 ms against
+ *     0.89, 1.82, 0.43, 2.29 and 7.42: 0.03 to 0.15.  With `expected` uploaded from host memory in front of the call
+ *     (24 bytes per object) it is 0.03 to 0.16.  One table outside those shapes has the host path ahead: see below;
+ *   - the host path is nearest at 4096 x 64, where it picks only 4096 sums out of the 7 MB it copies;
+ *   - the call alone takes 15 to 19 us of device time (a memset and three kernels), the 32-byte records 0.1 to 1.2 us
+ *     more: launches, not bytes.  What verify takes beyond it is the synchronise and two small copies;
+ *   - a caller that wants every digest on the host anyway (sha1_hex() of every object) still copies them: results()
+ *     brings 32 bytes per object instead of 28 per extent, which was not timed here;
+ *   - all of the figures above are for tables WITHOUT failed members, where the per-extent pass takes no owner search
+ *     and no atomic minimum.  With a failed member in 1 % of the objects the call takes 17 to 26 us and verify stays at
+ *     0.02 to 0.15 of the host path; with EVERY member failed (4 to 64 atomic minima on each word) the call takes 26
+ *     to 67 us and verify 0.05 to 0.19 of the host path (0.40 ms against 7.9 at 262 144 x 4);
+ *   - the HOST PATH IS AHEAD in one case: ONE object that owns all 1 048 576 extents with EVERY member failed.  All
+ *     1 048 576 atomic minima then fall on one word and the call takes 11.9 ms, against 1.0 ms for the host path;
+ *     the same table with no failed member takes 15 us (verify 0.051 ms against 0.95).  Such a table is a chain
+ *     that broke at its first member; a reduction over the wavefront in front of the atomic would take the count
+ *     to one per wavefront and is not built.  A caller that expects most members of very long objects to have
+ *     failed reads the statuses back instead. */
+#define EFES_VERDICT_OK       0u /* every member EFES_OK, and every digest that was compared is equal */
+#define EFES_VERDICT_MISMATCH 1u /* every member EFES_OK, a compared digest differs */
+#define EFES_VERDICT_FAILED   2u /* some member's status is not EFES_OK */
+#define EFES_VERDICT_EMPTY    3u /* the object owns no extents: no job ran, nothing to compare */
+
+typedef struct efes_object_result {
+    uint8_t  sum[24];  /* the 24-byte sum of the object's LAST extent (SHA-1 Sum, then CRC big-endian) */
+    int32_t  status;   /* the status of the object's FIRST member that is not EFES_OK, else EFES_OK */
+    uint32_t verdict;  /* EFES_VERDICT_* */
+} efes_object_result;  /* 32 bytes */
+
+typedef struct efes_results {       /* a HOST struct of device addresses */
+    const uint8_t* expected;        /* 24 * nobjects, laid out like a sum, or NULL: nothing is compared */
+    uint32_t compare;               /* EFES_HASH_SHA1 (bytes 0..19) | EFES_HASH_CRC32 (bytes 20..23); 0 allowed */
+    uint32_t _reserved;             /* 0 */
+    efes_object_result* results;    /* nobjects, or NULL */
+    uint32_t* bad;                  /* nobjects words, or NULL: the objects with verdict MISMATCH or FAILED, ascending */
+    uint32_t* counts;               /* 4 words, required: counts[v] = objects with verdict v */
+} efes_results; /* 40 bytes */
+
+size_t efes_objects_results_scratch(uint32_t nobjects, uint32_t nextents);
+int efes_objects_results(efes_ctx* ctx, const efes_objects* in, const efes_results* req, void* scratch_device,
+                         size_t scratch_bytes, void* stream);
+int efes_objects_results_host(const efes_objects* in, const efes_results* req);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */
