@@ -116,6 +116,7 @@ EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING = 0x1, 0x2
 EFES_OBJECTS_MAX = EFES_HASH_CHAIN_MAX_JOBS
 EFES_OBJECTS_COPY_ALIGN = 256
 OBJECTS_SCAN_BLOCK = 1024  # kObjectsBlock of efes_objects.hip: lanes of one scan workgroup (the scans' seams)
+OBJECTS_ORDER_TILE = 1024  # kOrderTile of efes_objects_order.hip: pairs of one sort workgroup (the sort's seams)
 EXTENT_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8")])
 assert ctypes.sizeof(Extent) == 16 == EXTENT_DTYPE.itemsize and ctypes.sizeof(Objects) == 96 and ctypes.sizeof(ObjectsOut) == 32
 
@@ -240,6 +241,12 @@ SIGNATURES = {
     "efes_objects_results_scratch": (_S, [_U32, _U32]),
     "efes_objects_results": (_I, [_VP, _P(Objects), _P(Results), _VP, _S, _VP]),
     "efes_objects_results_host": (_I, [_P(Objects), _P(Results)]),
+    "efes_objects_order_scratch": (_S, [_U32, _U32]),
+    "efes_objects_order": (_I, [_VP, _P(Objects), _VP, _VP, _S, _VP]),
+    "efes_objects_order_host": (_I, [_P(Objects), _VP]),
+    "efes_objects_jobs_ordered_scratch": (_S, [_U32, _U32]),
+    "efes_objects_jobs_ordered": (_I, [_VP, _P(Objects), _P(ObjectsOut), _VP, _VP, _VP, _S, _VP]),
+    "efes_objects_jobs_ordered_host": (_I, [_P(Objects), _P(ObjectsOut), _VP, _VP]),
     "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),

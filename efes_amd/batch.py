@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_HASH_CRC32, EFES_HASH_SHA1, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
                    MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Objects, ObjectsOut, Plan, PlanPart, Results)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_scratch, objects_results_scratch
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_ordered_scratch, objects_jobs_scratch, objects_order_scratch, objects_results_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -275,6 +275,16 @@ class DeviceObjects:
     "host" (copy_offsets, copy_bytes and jobs_host are read back from the device on first use).
     from_table() builds the set from a table that already lies in device memory.
 
+    order (build="device" and from_table() only; anything but "table" with build="host" raises ValueError) chooses
+    the order of the objects in the job array, which decides how the walks draw them.  "table" (the default) is
+    the table's own; "longest_first" ranks the objects by byte size on the device (efes_objects_order) and emits
+    them in that order (efes_objects_jobs_ordered), on torch's current stream with no wait; a device tensor of
+    nobjects 32-bit integers is the caller's own permutation.  What the walks write is in TABLE order whatever
+    the job order, so every accessor returns what it returns for "table"; order_host() is the permutation,
+    job_first_host() the slots of every rank and jobs_host the records in slot order.  Measured on shuffled
+    tables, "longest_first" made no walk faster and two slower (efes_hash.h "Object order"): it is for a caller
+    that wants that order for its own reasons, not a default.
+
     verify(expected) and results() sort the per-extent sums and statuses out per object ON THE DEVICE
     (efes_objects_results): verdicts against expected digests, the ascending list of the objects that are not in
     order and four counters, of which verify() copies only the counters and the list to the host.
@@ -285,9 +295,10 @@ class DeviceObjects:
     def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                  crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                 copy_offsets=None, checkpoints: bool = False, build: str = "host"):
+                 copy_offsets=None, checkpoints: bool = False, build: str = "host", order="table"):
         if build not in ("host", "device"):
             raise ValueError(f'DeviceObjects: build={build!r} (build="host" or build="device")')
+        DeviceObjects._check_order(order, build)
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
         if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
@@ -324,7 +335,7 @@ class DeviceObjects:
                                   torch.from_numpy(bounds.view(np.int32)).to(device), int((counts > 0).sum()), crcs=crcs,
                                   fresh=fresh, running=running, states=states, walk=walk, copy_to=copy_to,
                                   copy_offsets=None if offs is None else torch.from_numpy(offs.view(np.int64)).to(device),
-                                  checkpoints=checkpoints)
+                                  checkpoints=checkpoints, order=order)
             return
         owner = np.repeat(np.arange(self.nobjects, dtype=np.uint64), counts)
         self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
@@ -390,7 +401,7 @@ class DeviceObjects:
     def from_table(cls, data_ptr: int, extents, first, *, crcs: np.ndarray | None = None, fresh: bool = True,
                    running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                    crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                   copy_offsets=None, checkpoints: bool = False) -> "DeviceObjects":
+                   copy_offsets=None, checkpoints: bool = False, order="table") -> "DeviceObjects":
         """The set of an object table that already lies in DEVICE memory: `extents`, a contiguous torch tensor of
         shape (n, 2) of 64-bit integers, (offset, length) per extent, and `first`, one of shape (nobjects + 1,)
         of 32-bit integers, object i owning the extents [first[i], first[i + 1]).  The other arguments are the
@@ -398,7 +409,10 @@ class DeviceObjects:
         never copied to the host while the set is built or submitted (efes_objects_jobs expands it in stream
         order); first, last, copy_offsets and copy_bytes are fetched when first read, which sha1_hex() does.
         walk="auto" and "auto_wide" need the number of objects that have extents on the host and raise
-        ValueError: pass "wide", None or an EFES_MODE_* constant."""
+        ValueError: pass "wide", None or an EFES_MODE_* constant.  order as for the constructor: "longest_first"
+        ranks the objects on the device, so a table straight from a device-side pool is walked longest first
+        without ever visiting the host."""
+        DeviceObjects._check_order(order, "device")
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
         if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
@@ -425,14 +439,27 @@ class DeviceObjects:
         self.device = device
         self.nobjects, self.n = int(first.numel()) - 1, int(extents.shape[0])
         self._build_on_device(data_ptr, extents, first, None, crcs=crcs, fresh=fresh, running=running, states=states,
-                              walk=walk, copy_to=copy_to, copy_offsets=copy_offsets, checkpoints=checkpoints)
+                              walk=walk, copy_to=copy_to, copy_offsets=copy_offsets, checkpoints=checkpoints, order=order)
         return self
 
+    @staticmethod
+    def _check_order(order, build) -> None:
+        """order= checked from the arguments alone: no device is touched."""
+        if isinstance(order, str):
+            if order not in ("table", "longest_first"):
+                raise ValueError(f'DeviceObjects: order={order!r} (order="table", "longest_first" or a device tensor of nobjects '
+                                 "32-bit integers)")
+        elif not hasattr(order, "data_ptr") or order.dim() != 1 or order.element_size() != 4 or not order.is_contiguous():
+            raise ValueError('DeviceObjects: order is "table", "longest_first" or a contiguous device tensor of nobjects 32-bit integers')
+        if build == "host" and not (isinstance(order, str) and order == "table"):
+            raise ValueError('DeviceObjects: order= other than "table" needs build="device" (the host build emits table order)')
+
     def _build_on_device(self, data_ptr: int, ext, first, nchains, *, crcs, fresh, running, states, walk, copy_to,
-                         copy_offsets, checkpoints) -> None:
+                         copy_offsets, checkpoints, order="table") -> None:
         """The rest of a set whose arrays efes_objects_jobs makes: ext, first (and copy_offsets) are device
         tensors, kept until the set goes; the states, sums, statuses and records as the host build allocates
-        them; then the call on torch's current stream, with no wait behind it."""
+        them; then the call on torch's current stream, with no wait behind it.  With an order other than
+        "table": efes_objects_order (order="longest_first") and efes_objects_jobs_ordered instead, likewise."""
         torch, device, n, sha1 = self.torch, self.device, self.n, self.has_sha1
         self._table_ext, self._table_first, self._table_offsets = ext, first, copy_offsets
         self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
@@ -474,7 +501,37 @@ class DeviceObjects:
         out = ObjectsOut(jobs=self.jobs.data_ptr(), dst=self._dst.data_ptr() if copy_to is not None else None,
                          ckpt=self._ckpt_ptrs.data_ptr() if checkpoints else None,
                          layout=self._layout.data_ptr() if copy_to is not None else None)
-        self._ordered(lambda stream: self.ctx.objects_jobs(table, out, self._scratch.data_ptr(), self._scratch.numel(), stream))
+        if isinstance(order, str) and order == "table":
+            self._ordered(lambda stream: self.ctx.objects_jobs(table, out, self._scratch.data_ptr(), self._scratch.numel(), stream))
+            return
+        m = self.nobjects
+        rank = isinstance(order, str)  # "longest_first": the order is made here
+        if not rank and int(order.numel()) != m:
+            raise ValueError(f"DeviceObjects: order has {int(order.numel())} entries for {m} objects")
+        need = max(objects_jobs_ordered_scratch(m, n), objects_order_scratch(m, n) if rank else 0)
+        if need > self._scratch.numel():  # still one buffer for the order call, the builder and the walk behind them
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=device)
+        self._order = torch.empty(max(m, 1), dtype=torch.int32, device=device) if rank else order
+        self._job_first = torch.zeros(m + 1, dtype=torch.int32, device=device)
+        if rank:
+            self._ordered(lambda stream: self.ctx.objects_order(table, self._order.data_ptr(), self._scratch.data_ptr(),
+                                                                self._scratch.numel(), stream))
+        self._ordered(lambda stream: self.ctx.objects_jobs_ordered(table, out, self._order.data_ptr() or None, self._job_first.data_ptr(),
+                                                                   self._scratch.data_ptr(), self._scratch.numel(), stream))
+
+    def order_host(self) -> np.ndarray:
+        """The permutation the job array was emitted in: order_host()[r] is the table index of the object at rank
+        r (the identity for order="table").  Fetched from the device when called."""
+        if "_order" in self.__dict__:
+            return self._order.cpu().numpy().view(np.uint32)[: self.nobjects].copy()
+        return np.arange(self.nobjects, dtype=np.uint32)
+
+    def job_first_host(self) -> np.ndarray:
+        """nobjects + 1 slot boundaries: the jobs of the object at rank r are jobs_host[job_first_host()[r] :
+        job_first_host()[r + 1]] (the table's boundaries for order="table")."""
+        if "_job_first" in self.__dict__:
+            return self._job_first.cpu().numpy().view(np.uint32)[: self.nobjects + 1].copy()
+        return np.concatenate((self.first, [self.n])).astype(np.uint32)
 
     _FETCHED = ("first", "last", "copy_offsets", "copy_bytes", "jobs_host")
 

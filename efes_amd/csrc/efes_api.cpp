@@ -524,6 +524,40 @@ int efes_objects_results(efes_ctx* ctx, const efes_objects* in, const efes_resul
   return hip_err(efes::launch_objects_results(*in, *req, scratch, pick(ctx, stream)));
 }
 
+size_t efes_objects_order_scratch(uint32_t nobjects, uint32_t nextents) {
+  return efes::objects_order_scratch_bytes(nobjects, nextents);
+}
+
+int efes_objects_order(efes_ctx* ctx, const efes_objects* in, uint32_t* order, void* scratch, size_t scratch_bytes,
+                       void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::order_check(in, order);
+  if (rc != EFES_OK) return rc;
+  if (in->nobjects == 0) return EFES_OK;  // nothing to launch
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+      scratch_bytes < efes::objects_order_scratch_bytes(in->nobjects, in->nextents))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_objects_order(*in, order, scratch, pick(ctx, stream)));
+}
+
+size_t efes_objects_jobs_ordered_scratch(uint32_t nobjects, uint32_t nextents) {
+  return efes::objects_jobs_ordered_scratch_bytes(nobjects, nextents);
+}
+
+int efes_objects_jobs_ordered(efes_ctx* ctx, const efes_objects* in, const efes_objects_out* out, const uint32_t* order,
+                              uint32_t* job_first, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::ordered_check(in, out, order, job_first);
+  if (rc != EFES_OK) return rc;
+  if (in->nextents == 0 && !out->layout && !job_first) return EFES_OK;  // nothing to launch
+  if (in->nextents && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+                       scratch_bytes < efes::objects_jobs_ordered_scratch_bytes(in->nobjects, in->nextents)))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_objects_jobs_ordered(*in, *out, order, job_first, scratch, pick(ctx, stream)));
+}
+
 int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, uint32_t n, char* text, void* stream) {
   if (!ctx || n > EFES_HASH_CHAIN_MAX_JOBS) return EFES_ERR_ARG;
   if (n == 0) return EFES_OK;

@@ -195,6 +195,14 @@ hipError_t launch_objects_jobs(const efes_objects& in, const efes_objects_out& o
 // flags for the ascending list.  The arguments are checked by the caller (results_check, efes_objects_rules.hpp).
 size_t objects_results_scratch_bytes(uint32_t nobjects, uint32_t nextents);
 hipError_t launch_objects_results(const efes_objects& in, const efes_results& req, void* scratch, hipStream_t s);
+// Object order (efes_objects_order, efes_objects_jobs_ordered; efes_objects_order.hip): a stable LSD radix sort of
+// (~size, index) pairs whose passes skip themselves where all keys share the digit, and the builder with the
+// objects emitted in a given order.  The arguments are checked by the caller (order_check, ordered_check).
+size_t objects_order_scratch_bytes(uint32_t nobjects, uint32_t nextents);
+hipError_t launch_objects_order(const efes_objects& in, uint32_t* order, void* scratch, hipStream_t s);
+size_t objects_jobs_ordered_scratch_bytes(uint32_t nobjects, uint32_t nextents);
+hipError_t launch_objects_jobs_ordered(const efes_objects& in, const efes_objects_out& out, const uint32_t* order,
+                                       uint32_t* job_first, void* scratch, hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
 

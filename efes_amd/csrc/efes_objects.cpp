@@ -1,9 +1,11 @@
 // efes_objects.cpp -- efes_objects_jobs_host: the object table expanded into job records on the HOST
 // (efes_hash.h "Object tables").  The same rules as the device kernels (efes_objects_rules.hpp), one plain
 // loop each; the base addresses in the table are only added to, never dereferenced.  Behind it
-// efes_objects_results_host, the per-object results of such a table ("Object results"), likewise.
+// efes_objects_results_host, the per-object results of such a table ("Object results"), likewise; and
+// efes_objects_order_host and efes_objects_jobs_ordered_host ("Object order"), the ranking and the ordered build.
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "efes_objects_rules.hpp"
@@ -99,5 +101,101 @@ extern "C" int efes_objects_results_host(const efes_objects* in, const efes_resu
     if (req->bad && efes::results_is_bad(w[7])) req->bad[nbad++] = i;
   }
   memcpy(req->counts, counts, sizeof counts);
+  return EFES_OK;
+}
+
+// efes_objects_order_host: the longest-first ranking (efes_hash.h "Object order") on the HOST: the keys of
+// order_key over the sizes of order_size, as on the device, and a stable sort from the identity.
+extern "C" int efes_objects_order_host(const efes_objects* in, uint32_t* order) {
+  const int rc = efes::order_check(in, order);
+  if (rc != EFES_OK) return rc;
+  const uint32_t n = in->nextents, m = in->nobjects;
+  if (m == 0) return EFES_OK;
+  std::vector<uint64_t> E, key;
+  std::vector<uint32_t> idx;
+  try {
+    E.resize((size_t)n + 1);
+    key.resize(m);
+    idx.resize(m);
+  } catch (...) {
+    return EFES_ERR_NOMEM;
+  }
+  uint64_t at = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    E[j] = at;
+    at += in->extents[j].length;
+  }
+  E[n] = at;
+  for (uint32_t i = 0; i < m; ++i) {
+    key[i] = efes::order_key(efes::order_size(in->first, E.data(), i, n));
+    idx[i] = i;
+  }
+  try {
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  } catch (...) {  // its temporary buffer
+    return EFES_ERR_NOMEM;
+  }
+  memcpy(order, idx.data(), (size_t)m * sizeof(uint32_t));
+  return EFES_OK;
+}
+
+// efes_objects_jobs_ordered_host: efes_objects_jobs_host with the objects emitted in the order given.  The layout
+// is the table's, as there; every slot goes through order_slot, order_job_words and order_job_dst, as on the device.
+extern "C" int efes_objects_jobs_ordered_host(const efes_objects* in, const efes_objects_out* out, const uint32_t* order,
+                                              uint32_t* job_first) {
+  const int rc = efes::ordered_check(in, out, order, job_first);
+  if (rc != EFES_OK) return rc;
+  const uint32_t n = in->nextents, m = in->nobjects;
+  const bool want_layout = out->layout != nullptr, want_dst = n && in->copy_to;
+  if (!n && !want_layout && !job_first) return EFES_OK;
+  std::vector<uint64_t> E, L, J;
+  try {
+    E.resize((size_t)n + 1);
+    J.resize((size_t)m + 1);
+    if (!in->copy_offsets && (want_layout || want_dst)) L.resize((size_t)m + 1);
+  } catch (...) {
+    return EFES_ERR_NOMEM;
+  }
+  uint64_t at = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    E[j] = at;
+    at += in->extents[j].length;
+  }
+  E[n] = at;
+  const uint64_t align = efes::objects_align_of(in);
+  const uint64_t* layout = in->copy_offsets;
+  if (!layout && (want_layout || want_dst)) {
+    at = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+      L[i] = at;
+      at += efes::objects_round_up(efes::order_size(in->first, E.data(), i, n), align);
+    }
+    layout = L.data();
+  }
+  if (want_layout) {
+    uint64_t room = 0;
+    for (uint32_t i = 0; i < m; ++i) {
+      out->layout[i] = layout[i];
+      const uint64_t end = layout[i] + efes::order_size(in->first, E.data(), i, n);
+      if (in->copy_offsets ? end > room : i + 1 == m) room = end;
+    }
+    out->layout[m] = room;
+  }
+  at = 0;  // without extents every count is 0 and neither first[] nor order[] is read
+  for (uint32_t r = 0; r < m; ++r) {
+    J[r] = at;
+    if (n) at += efes::order_count(in->first, efes::order_object(order, m, r), n);
+  }
+  J[m] = at;
+  if (job_first)
+    for (uint32_t r = 0; r <= m; ++r) job_first[r] = efes::order_job_first(J[r], n);
+  for (uint32_t k = 0; k < n; ++k) {
+    const efes::OrderSlot s = efes::order_slot(in->first, order, J.data(), m, n, k);
+    uint64_t w[efes::kJobWords];
+    efes::order_job_words(*in, s.i, s.j, w);
+    memcpy(static_cast<void*>(out->jobs + k), w, sizeof w);
+    if (in->ckpt) out->ckpt[k] = in->ckpt + s.j;
+    if (want_dst) out->dst[k] = (void*)(uintptr_t)efes::order_job_dst(*in, E.data(), layout, s.i, s.j);
+  }
   return EFES_OK;
 }

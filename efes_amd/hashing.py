@@ -25,7 +25,7 @@ import numpy as np
 
 from ._lib import MODE_AUTO, EfesError, Objects, ObjectsOut, PairStats, Plan, QueueStats, Results, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "objects_order_scratch", "objects_order_host", "objects_jobs_ordered_scratch", "objects_jobs_ordered_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -103,6 +103,31 @@ def objects_results_host(table: Objects, req: Results) -> None:
     """efes_objects_results_host: objects_results() on the host -- first, sums and status of `table` and every
     array of `req` are host addresses.  Needs no GPU."""
     check(lib().efes_objects_results_host(ctypes.byref(table), ctypes.byref(req)), "efes_objects_results_host")
+
+
+def objects_order_scratch(nobjects: int, nextents: int) -> int:
+    """efes_objects_order_scratch: device bytes efes_objects_order needs for a table of nobjects objects and
+    nextents extents (0 where either exceeds EFES_OBJECTS_MAX, never 0 otherwise)."""
+    return int(lib().efes_objects_order_scratch(nobjects, nextents))
+
+
+def objects_order_host(table: Objects, order_ptr: int | None) -> None:
+    """efes_objects_order_host: objects_order() on the host -- extents and first of `table` and the nobjects
+    32-bit words at order_ptr are host addresses.  Needs no GPU."""
+    check(lib().efes_objects_order_host(ctypes.byref(table), order_ptr), "efes_objects_order_host")
+
+
+def objects_jobs_ordered_scratch(nobjects: int, nextents: int) -> int:
+    """efes_objects_jobs_ordered_scratch: device bytes efes_objects_jobs_ordered needs for a table of nobjects
+    objects and nextents extents (0 where either exceeds EFES_OBJECTS_MAX, never 0 otherwise)."""
+    return int(lib().efes_objects_jobs_ordered_scratch(nobjects, nextents))
+
+
+def objects_jobs_ordered_host(table: Objects, out: ObjectsOut, order_ptr: int | None, job_first_ptr: int | None = None) -> None:
+    """efes_objects_jobs_ordered_host: objects_jobs_ordered() on the host -- the arrays of objects_jobs_host(), the
+    nobjects words of the order and the nobjects + 1 words of job_first (or None) are host addresses."""
+    check(lib().efes_objects_jobs_ordered_host(ctypes.byref(table), ctypes.byref(out), order_ptr, job_first_ptr),
+          "efes_objects_jobs_ordered_host")
 
 
 class Context:
@@ -212,6 +237,24 @@ class Context:
         chain call queued behind it on the same stream needs no synchronisation in between."""
         check(lib().efes_objects_jobs(self.handle, ctypes.byref(table), ctypes.byref(out), scratch_ptr, scratch_bytes,
                                       stream), "efes_objects_jobs")
+
+    def objects_order(self, table: Objects, order_ptr: int | None, scratch_ptr: int | None, scratch_bytes: int,
+                      stream: int | None = None) -> None:
+        """efes_objects_order: the longest-first ranking of the objects of `table` (only its extents' lengths, its
+        first[] and its counts are read) into the nobjects 32-bit words at the device address order_ptr --
+        descending byte size, equal sizes in ascending table index --, sorted on the device; asynchronous on
+        `stream`; scratch: objects_order_scratch(nobjects, nextents) device bytes, 16-byte aligned."""
+        check(lib().efes_objects_order(self.handle, ctypes.byref(table), order_ptr, scratch_ptr, scratch_bytes, stream),
+              "efes_objects_order")
+
+    def objects_jobs_ordered(self, table: Objects, out: ObjectsOut, order_ptr: int | None, job_first_ptr: int | None,
+                             scratch_ptr: int | None, scratch_bytes: int, stream: int | None = None) -> None:
+        """efes_objects_jobs_ordered: objects_jobs() with the objects emitted in the order of the nobjects 32-bit
+        words at the device address order_ptr (objects_order()'s, or the caller's own permutation); job_first_ptr:
+        None, or nobjects + 1 device words for the first slot of every rank.  What the walks write stays in table
+        order; scratch: objects_jobs_ordered_scratch(nobjects, nextents) device bytes."""
+        check(lib().efes_objects_jobs_ordered(self.handle, ctypes.byref(table), ctypes.byref(out), order_ptr, job_first_ptr,
+                                              scratch_ptr, scratch_bytes, stream), "efes_objects_jobs_ordered")
 
     def objects_results(self, table: Objects, req: Results, scratch_ptr: int | None, scratch_bytes: int,
                         stream: int | None = None) -> None:

@@ -998,6 +998,105 @@ int efes_objects_results(efes_ctx* ctx, const efes_objects* in, const efes_resul
                          size_t scratch_bytes, void* stream);
 int efes_objects_results_host(const efes_objects* in, const efes_results* req);
 
+/* Object order: the LONGEST-FIRST order of an object table's chains, made ON THE DEVICE.  Every walk depends on
+ * the order of the chains in its job array: the wide walk gives 64 consecutive chains to one wavefront, which
+ * lasts as long as its longest member in every round, and the wave and grouped walks draw whole chains from the
+ * array in order, so long chains at the end leave the launch on a few busy SIMDs.  efes_plan_batch orders host
+ * jobs by host lengths; for an object table efes_objects_order ranks the objects by size and
+ * efes_objects_jobs_ordered emits the job array in that (or any) order, both in stream order in front of the walk.
+ * The builder's records address the states by object index and the sums, statuses and records by table extent
+ * index, so only the job array and its two parallel pointer arrays are permuted: everything the walks write stays
+ * in TABLE order, and efes_objects_results and the gather layout work on an ordered set unchanged.
+ *
+ * efes_objects_order writes order[0, nobjects): order[r] is the table index of the object at rank r.  The key of
+ * object i is its byte size as the builder computes it, E[bound(first, i + 1)] - E[bound(first, i)] modulo 2^64,
+ * E the running sum of the lengths and bound() the clamp of first[] to [0, nextents].  Descending size; equal
+ * sizes in ascending table index: a total order, so the result is one fixed permutation and the device call and
+ * the host twin give the same words.  Only extents[].length, first, nobjects and nextents of `in` are read, never
+ * the data or the other base addresses.
+ * SAFETY PROPERTY: whatever first[] holds, order is a permutation of [0, nobjects).
+ * Errors, checked first and without the device: EFES_ERR_ARG for a NULL ctx or in, nobjects or nextents >
+ * EFES_OBJECTS_MAX; with nextents > 0 a NULL extents; with nobjects > 0 a NULL first, a NULL or not 4-byte aligned
+ * order, and a scratch that is NULL, not 16-byte aligned or smaller than efes_objects_order_scratch(nobjects,
+ * nextents) (0 for counts the call refuses, never 0 otherwise).  A refused call writes nothing.  nobjects == 0
+ * returns EFES_OK, launches nothing and writes nothing; with nextents == 0 every size is 0 and the order is the
+ * identity.
+ * Asynchronous on `stream` (NULL = the context stream), no host read-back, allocation or wait; the scratch is used
+ * in stream order.
+ * A stable LSD radix sort of (key = bitwise NOT of the size, value = object index) pairs, radix 256, from the
+ * identity, so stability gives the tie rule.  Each digit pass is three launches -- the digit counts of every tile
+ * of 1024 pairs, the two-level scan of those counts, a stable scatter (ranks within a wavefront by ballots, across
+ * the tile's wavefronts by a table in LDS) -- and no wave waits for another.  Real sizes fill two or three of the
+ * eight key bytes: the pass that makes the keys also ORs key[i] ^ key[0] over all i into one word, and the
+ * launches of a digit in which all keys agree return at once; which of the two buffers a pass reads follows on
+ * the device from that word.  The number of launches is fixed by the counts (DESIGN.md §4 "Object order").
+ *
+ * efes_objects_jobs_ordered is efes_objects_jobs that emits the objects in the order given: the output of
+ * efes_objects_order or any permutation the caller has (its own priority order).  The whole contract of
+ * efes_objects_jobs holds, with the same table and the same argument errors; in addition EFES_ERR_ARG for a NULL
+ * order with nobjects > 0 and for an order or job_first that is not 4-byte aligned, and the scratch is measured by
+ * efes_objects_jobs_ordered_scratch.  Let cnt(i) = bound(first, i + 1) - bound(first, i), 0 where that is
+ * negative, and J[r] the exclusive prefix sum of cnt(order[r]).  Slot k in [J[r], J[r + 1]) belongs to object
+ * i = order[r], extent j = bound(first, i) + (k - J[r]):
+ *   - jobs[k] is, byte for byte, the record efes_objects_jobs writes at jobs[j]: the same data, length, sha1 + i,
+ *     crc32 + i, sums + 24 j, status + j and flag word;
+ *   - out->dst[k] and out->ckpt[k] are the values efes_objects_jobs writes at dst[j] and ckpt[j];
+ *   - out->layout is unchanged: the gather layout is a property of the table, not of the job order;
+ *   - job_first (may be NULL; else nobjects + 1 words): job_first[r] = J[r], saturated at nextents -- the slots a
+ *     rank owns.  Without extents it is all zeros.
+ * With the identity order and a well-formed table every output is byte for byte that of efes_objects_jobs.
+ * SAFETY PROPERTY, as for the builder: order[r] is clamped into [0, nobjects), the rank of a slot is an index of
+ * that range, j is clamped into [0, nextents), and every slot k < nextents is written.  An order that is not a
+ * permutation, or a malformed first[], gives unspecified but in-range jobs that must not be run.
+ * Asynchronous and stream-ordered like the builder: a chain call queued behind it on the same stream needs no
+ * host synchronisation.  The scans of the lengths and of the rounded sizes are the builder's; added are a scan of
+ * cnt(order[r]) and a fill pass of one lane per output SLOT: a binary search of J for the rank, then the builder's
+ * LDS-staged, wavefront-contiguous stores of the seven job words.
+ *
+ * The two _host twins are the same functions over HOST arrays, with no context, scratch or stream, like
+ * efes_objects_jobs_host; EFES_ERR_NOMEM if their working arrays cannot be had.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/objects_order/bench.json; DESIGN.md §4 "Object order" has the table; fused sets
+ * over a 4 GiB pool whose tables were SHUFFLED by a fixed seed, walked by the call DeviceObjects(walk="auto_wide")
+ * picks; device time, medians; "table" = efes_objects_jobs + the walk, "ordered" = efes_objects_order +
+ * efes_objects_jobs_ordered + the walk, the project's rule: a median below the other path's minimum):
+ *   - the expected gain is NOT there: on none of the four shapes is the longest-first order faster than the shuffled
+ *     table's own, and on two it is slower.  The walk alone over longest-first jobs takes 1.12 times its time over the
+ *     shuffled jobs on the ragged wide-walk set (65 536 objects of 1-8 extents of 4-64 KiB: 15.98 ms against 14.31),
+ *     1.05 times on the ragged grouped-walk set (4096 objects of 1-16 extents of 4-256 KiB, EFES_MODE_GROUP16: 38.06
+ *     against 36.20), and the same within the spread on the ragged wave-walk set (1024 objects of 1-64 extents of
+ *     4 KiB-1 MiB: 448.9 against 447.9) and on 65 536 x 4 x 16 KiB (2.743 against 2.734).  With the two calls in
+ *     front, "ordered" takes 1.04, 1.05, 1.003 and 1.03 times "table"; the table-order median is below the ordered
+ *     minimum on the three ragged shapes.  So order="table" stays the default, and a table in upload order or straight
+ *     from a pool is best walked as it is;
+ *   - the walk over the device-ordered jobs equals the walk over a table sorted on the host beforehand (1.00 on
+ *     every shape: the same job order), and that is the figure the ragged rows of the chain sections quote: the 15.9 ms
+ *     of the ragged wide-walk row is 1.12 times what the same set takes shuffled.  "Arrays sorted longest first suit
+ *     it" (efes_hash_chain_wide) is not what this run shows against a random order; it was never measured against one;
+ *   - what the calls cost: efes_objects_order 91, 79, 77 and 77 us of device time on the four shapes (some thirty
+ *     launches of a few microseconds, most of which return at once: real sizes fill three key bytes),
+ *     efes_objects_jobs_ordered 43, 52, 50 and 57 us (minima 30, 21, 20 and 26): together 0.8 %, 0.3 %, 0.03 % and
+ *     4.9 % of the walk behind them.  On the equal shape, where no order can gain, that 4.9 % is the whole effect;
+ *   - a caller that WANTS a given order -- longest first for a consumer that drains results in that order, its own
+ *     priority order through efes_objects_jobs_ordered -- gets it without the round trip: against copying the table
+ *     to the host, a numpy stable sort, permuting and uploading it and efes_objects_jobs, wall-clock from the table
+ *     on the device to the synchronise behind the walk, 15.8 ms against 30.4 (minimum 24.1) on the ragged wide-walk
+ *     set and 2.84 against 5.24 on 65 536 x 4 x 16 KiB, the median below the host path's minimum; 38.2 against 38.9
+ *     on the grouped-walk set, also below its minimum; no difference on the wave-walk set (449.2 against 449.1), whose
+ *     walk hides both.  And only this path leaves the sums, statuses and results in TABLE order: the host path
+ *     permutes the table, so everything comes back in sorted order. */
+size_t efes_objects_order_scratch(uint32_t nobjects, uint32_t nextents);
+int efes_objects_order(efes_ctx* ctx, const efes_objects* in, uint32_t* order_device, void* scratch_device,
+                       size_t scratch_bytes, void* stream);
+int efes_objects_order_host(const efes_objects* in, uint32_t* order);
+
+size_t efes_objects_jobs_ordered_scratch(uint32_t nobjects, uint32_t nextents);
+int efes_objects_jobs_ordered(efes_ctx* ctx, const efes_objects* in, const efes_objects_out* out,
+                              const uint32_t* order_device, uint32_t* job_first_device, void* scratch_device,
+                              size_t scratch_bytes, void* stream);
+int efes_objects_jobs_ordered_host(const efes_objects* in, const efes_objects_out* out, const uint32_t* order,
+                                   uint32_t* job_first);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */
