@@ -136,6 +136,18 @@ EFES_VERDICT_OK, EFES_VERDICT_MISMATCH, EFES_VERDICT_FAILED, EFES_VERDICT_EMPTY 
 OBJECT_RESULT_DTYPE = np.dtype([("sum", "u1", (24,)), ("status", "<i4"), ("verdict", "<u4")])
 assert ctypes.sizeof(ObjectResult) == 32 == OBJECT_RESULT_DTYPE.itemsize and ctypes.sizeof(Results) == 40
 
+
+class Infos(ctypes.Structure):
+    """efes_infos: the `.info` texts of n objects and the states they decode into (efes_infos_unmarshal_text,
+    efes_infos_marshal_text); a host struct of device addresses (host ones for the _host twins)."""
+    _fields_ = [("text", ctypes.c_void_p), ("sha1", ctypes.c_void_p), ("crc32", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
+EFES_INFO_TEXT_BYTES = 208  # 200 characters of the SHA-1 state's MarshalText, then 8 of the CRC's
+EFES_SHA1_NX_REFUSED = 65   # nx of the refusing state an invalid text leaves: every Write into it gets EFES_ERR_STATE
+assert ctypes.sizeof(Infos) == 48
+
 assert ctypes.sizeof(Sha1State) == 104 and ctypes.sizeof(Job) == 56 and ctypes.sizeof(QueueStats) == 32
 assert ctypes.sizeof(PairStats) == 32
 
@@ -248,6 +260,10 @@ SIGNATURES = {
     "efes_objects_jobs_ordered": (_I, [_VP, _P(Objects), _P(ObjectsOut), _VP, _VP, _VP, _S, _VP]),
     "efes_objects_jobs_ordered_host": (_I, [_P(Objects), _P(ObjectsOut), _VP, _VP]),
     "efes_checkpoints_marshal_text": (_I, [_VP, _VP, _U32, _VP, _VP]),
+    "efes_infos_unmarshal_text": (_I, [_VP, _P(Infos), _VP]),
+    "efes_infos_marshal_text": (_I, [_VP, _P(Infos), _VP]),
+    "efes_infos_unmarshal_text_host": (_I, [_P(Infos)]),
+    "efes_infos_marshal_text_host": (_I, [_P(Infos)]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),
     "efes_crc32_state_marshal_text": (None, [_P(Crc32State), _VP]),

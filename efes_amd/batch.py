@@ -9,8 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_HASH_CRC32, EFES_HASH_SHA1, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
-                   MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Objects, ObjectsOut, Plan, PlanPart, Results)
+from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_HASH_CRC32, EFES_HASH_SHA1, EFES_INFO_TEXT_BYTES, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
+                   MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Infos, Objects, ObjectsOut, Plan, PlanPart, Results)
 from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_ordered_scratch, objects_jobs_scratch, objects_order_scratch, objects_results_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
@@ -285,6 +285,17 @@ class DeviceObjects:
     tables, "longest_first" made no walk faster and two slower (efes_hash.h "Object order"): it is for a caller
     that wants that order for its own reasons, not a default.
 
+    infos (instead of states= and crcs=; implies fresh=False) resumes every object from its `.info` texts, decoded ON
+    THE DEVICE (efes_infos_unmarshal_text) into the initial states on torch's current stream, in front of the builder
+    and with no wait: a device uint8 tensor of nobjects x 208 characters (info_texts(device=True) of an earlier
+    round), a host (nobjects, 208) uint8 array, or a list of (sha1_text, crc32_text) byte pairs.  A text with a
+    character that is no hex digit -- a pair of the wrong length becomes a row of b"?" -- leaves the REFUSING state:
+    that object's members all get EFES_ERR_STATE, nothing of it is gathered, results() gives EFES_VERDICT_FAILED,
+    and the other objects run.  A CRC-only set has no refusing state: the CRC of a broken text starts from 0, so
+    such a caller reads resume_counts() or resume_status_host() before it trusts the CRCs.  reset() restores the
+    decoded states without decoding again.  info_texts() marshals the states every object has NOW (after a run: the
+    texts its `.info` holds next) on the device, for every set, with or without checkpoints=True.
+
     verify(expected) and results() sort the per-extent sums and statuses out per object ON THE DEVICE
     (efes_objects_results): verdicts against expected digests, the ascending list of the objects that are not in
     order and four counters, of which verify() copies only the counters and the list to the host.
@@ -292,12 +303,14 @@ class DeviceObjects:
 
     _ordered = DeviceBatch._ordered
 
-    def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool = True,
+    def __init__(self, data_ptr: int, objects, *, crcs: np.ndarray | None = None, fresh: bool | None = None,
                  running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                  crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                 copy_offsets=None, checkpoints: bool = False, build: str = "host", order="table"):
+                 copy_offsets=None, checkpoints: bool = False, build: str = "host", order="table", infos=None):
         if build not in ("host", "device"):
             raise ValueError(f'DeviceObjects: build={build!r} (build="host" or build="device")')
+        objects = [list(o) for o in objects]
+        fresh, infos = DeviceObjects._check_infos(infos, fresh, states, crcs, len(objects))
         DeviceObjects._check_order(order, build)
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
@@ -320,7 +333,6 @@ class DeviceObjects:
         self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
         self.torch = torch
         self.device = device
-        objects = [list(o) for o in objects]
         self.nobjects = len(objects)
         counts = np.array([len(o) for o in objects], dtype=np.int64)
         n = self.n = int(counts.sum())
@@ -335,12 +347,15 @@ class DeviceObjects:
                                   torch.from_numpy(bounds.view(np.int32)).to(device), int((counts > 0).sum()), crcs=crcs,
                                   fresh=fresh, running=running, states=states, walk=walk, copy_to=copy_to,
                                   copy_offsets=None if offs is None else torch.from_numpy(offs.view(np.int64)).to(device),
-                                  checkpoints=checkpoints, order=order)
+                                  checkpoints=checkpoints, order=order, infos=infos)
             return
         owner = np.repeat(np.arange(self.nobjects, dtype=np.uint64), counts)
-        self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
-        assert self.init_crcs.size == self.nobjects
-        self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
+        if infos is not None:
+            self._resume_from_infos(infos)
+        else:
+            self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
+            assert self.init_crcs.size == self.nobjects
+            self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
         self.crcs = self._init_crcs_dev.clone() if self.nobjects else torch.zeros(4, dtype=torch.uint8, device=device)
         self.sums = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=device)
         self.status = torch.full((max(n, 1),), -99, dtype=torch.int32, device=device)
@@ -351,9 +366,10 @@ class DeviceObjects:
         if crc32:
             jobs["crc32"] = np.uint64(self.crcs.data_ptr()) + owner * np.uint64(4)
         if sha1:
-            self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
-            assert self.init_states.size == self.nobjects
-            self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
+            if infos is None:
+                self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
+                assert self.init_states.size == self.nobjects
+                self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
             self.states = self._init_states_dev.clone() if self.nobjects else torch.zeros(104, dtype=torch.uint8, device=device)
             jobs["sha1"] = np.uint64(self.states.data_ptr()) + owner * np.uint64(104)
         jobs["sum"] = np.uint64(self.sums.data_ptr()) + idx * np.uint64(24)
@@ -398,10 +414,10 @@ class DeviceObjects:
         torch.cuda.synchronize(device)
 
     @classmethod
-    def from_table(cls, data_ptr: int, extents, first, *, crcs: np.ndarray | None = None, fresh: bool = True,
+    def from_table(cls, data_ptr: int, extents, first, *, crcs: np.ndarray | None = None, fresh: bool | None = None,
                    running: bool = False, ctx: Context | None = None, device: str = "cuda:0", sha1: bool = False,
                    crc32: bool = True, states: np.ndarray | None = None, walk=None, copy_to: int | None = None,
-                   copy_offsets=None, checkpoints: bool = False, order="table") -> "DeviceObjects":
+                   copy_offsets=None, checkpoints: bool = False, order="table", infos=None) -> "DeviceObjects":
         """The set of an object table that already lies in DEVICE memory: `extents`, a contiguous torch tensor of
         shape (n, 2) of 64-bit integers, (offset, length) per extent, and `first`, one of shape (nobjects + 1,)
         of 32-bit integers, object i owning the extents [first[i], first[i + 1]).  The other arguments are the
@@ -411,7 +427,8 @@ class DeviceObjects:
         walk="auto" and "auto_wide" need the number of objects that have extents on the host and raise
         ValueError: pass "wide", None or an EFES_MODE_* constant.  order as for the constructor: "longest_first"
         ranks the objects on the device, so a table straight from a device-side pool is walked longest first
-        without ever visiting the host."""
+        without ever visiting the host.  infos as for the constructor: with a device tensor of texts neither the
+        table nor the states ever visit the host."""
         DeviceObjects._check_order(order, "device")
         if checkpoints and not sha1:
             raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
@@ -429,6 +446,7 @@ class DeviceObjects:
             raise ValueError("DeviceObjects.from_table: extents is a contiguous (n, 2) tensor of 64-bit integers")
         if first.dim() != 1 or first.numel() < 1 or first.element_size() != 4 or not first.is_contiguous():
             raise ValueError("DeviceObjects.from_table: first is a contiguous (nobjects + 1,) tensor of 32-bit integers")
+        fresh, infos = DeviceObjects._check_infos(infos, fresh, states, crcs, int(first.numel()) - 1)
         import torch
 
         self = cls.__new__(cls)
@@ -439,8 +457,93 @@ class DeviceObjects:
         self.device = device
         self.nobjects, self.n = int(first.numel()) - 1, int(extents.shape[0])
         self._build_on_device(data_ptr, extents, first, None, crcs=crcs, fresh=fresh, running=running, states=states,
-                              walk=walk, copy_to=copy_to, copy_offsets=copy_offsets, checkpoints=checkpoints, order=order)
+                              walk=walk, copy_to=copy_to, copy_offsets=copy_offsets, checkpoints=checkpoints, order=order,
+                              infos=infos)
         return self
+
+    @staticmethod
+    def _check_infos(infos, fresh, states, crcs, nobjects: int):
+        """(fresh, infos) of the infos= and fresh= arguments, checked from the arguments alone: no device is touched.
+        infos comes back as None, as the caller's device tensor, or as a host (nobjects, 208) uint8 array; a list of
+        (sha1_text, crc32_text) pairs is packed into one, a pair of the wrong length as a row of b"?"."""
+        if infos is None:
+            return (True if fresh is None else bool(fresh)), None
+        if fresh:
+            raise ValueError("DeviceObjects: infos= resumes the objects from their `.info` texts; fresh=True starts them anew")
+        if states is not None or crcs is not None:
+            raise ValueError("DeviceObjects: infos= gives the initial states; states= and crcs= do not go with it")
+        want = f"DeviceObjects: infos is {nobjects} x {EFES_INFO_TEXT_BYTES} uint8 characters (a device tensor, a host array of that shape) or {nobjects} (sha1_text, crc32_text) pairs"
+        if hasattr(infos, "data_ptr"):
+            if str(infos.dtype) != "torch.uint8" or int(infos.numel()) != nobjects * EFES_INFO_TEXT_BYTES or not infos.is_contiguous():
+                raise ValueError(f"{want} (got a {infos.dtype} tensor of shape {tuple(infos.shape)})")
+            return False, infos
+        if isinstance(infos, np.ndarray):
+            if infos.dtype != np.uint8 or infos.shape != (nobjects, EFES_INFO_TEXT_BYTES):
+                raise ValueError(f"{want} (got {infos.dtype} {infos.shape})")
+            return False, np.ascontiguousarray(infos)
+        pairs = list(infos)
+        if len(pairs) != nobjects or any(not isinstance(p, (tuple, list)) or len(p) != 2 for p in pairs):
+            raise ValueError(f"{want} (got {len(pairs)} entries)")
+        rows = np.full((nobjects, EFES_INFO_TEXT_BYTES), ord("?"), np.uint8)
+        for i, (a, b) in enumerate(pairs):
+            a, b = (t.encode() if isinstance(t, str) else bytes(t) for t in (a, b))
+            if len(a) == 200 and len(b) == 8:  # any other length: errInvalidDigest in Go, the refusing row here
+                rows[i] = np.frombuffer(a + b, np.uint8)
+        return False, rows
+
+    def _resume_from_infos(self, infos) -> None:
+        """The initial states decoded from the texts by efes_infos_unmarshal_text, on torch's current stream and with
+        no wait: _init_crcs_dev and _init_states_dev as the other constructors leave them, so reset() restores the
+        decoded states; the per-object statuses and the two counters stay on the device until asked for."""
+        torch, device, m = self.torch, self.device, self.nobjects
+        text = infos if hasattr(infos, "data_ptr") else torch.from_numpy(infos.reshape(-1)).to(device)
+        if str(text.device) != str(torch.device(device)):
+            text = text.to(device)
+        if text.data_ptr() & 7:  # a view into a larger tensor: the call reads 8 characters at a time
+            text = text.clone()
+        self.init_crcs = self.init_states = None  # known on the device only
+        self._init_crcs_dev = torch.zeros(m * 4, dtype=torch.uint8, device=device)
+        if self.has_sha1:
+            self._init_states_dev = torch.empty(m * SHA1_STATE_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self._resume_status = torch.zeros(max(m, 1), dtype=torch.int32, device=device)
+        self._resume_counts = torch.zeros(2, dtype=torch.int32, device=device)
+        self._resume_text = text  # alive until the set goes: the call that reads it is only queued
+        req = Infos(text=text.data_ptr() or None, sha1=(self._init_states_dev.data_ptr() or None) if self.has_sha1 else None,
+                    crc32=(self._init_crcs_dev.data_ptr() or None) if self.has_crc32 else None,
+                    status=self._resume_status.data_ptr(), counts=self._resume_counts.data_ptr(), n=m)
+        self._ordered(lambda stream: self.ctx.infos_unmarshal_text(req, stream))
+
+    def _need_infos(self, what: str) -> None:
+        if "_resume_counts" not in self.__dict__:
+            raise ValueError(f"{what}: build the set with infos=")
+
+    def resume_counts(self) -> tuple:
+        """(valid, invalid): how many of the infos= texts decoded and how many left the refusing state (8 bytes read
+        back)."""
+        self._need_infos("resume_counts")
+        c = self._resume_counts.cpu().numpy().view(np.uint32)
+        return int(c[0]), int(c[1])
+
+    def resume_status_host(self) -> np.ndarray:
+        """Per object: EFES_OK, or EFES_ERR_INVALID_DIGEST for an infos= text with a character that is no hex digit."""
+        self._need_infos("resume_status_host")
+        return self._resume_status.cpu().numpy()[: self.nobjects].copy()
+
+    def info_texts(self, device: bool = False):
+        """Per object: the `.info` texts of the states and CRCs the set holds now, marshalled on the device by
+        efes_infos_marshal_text on torch's current stream (behind a run: what `.info` holds after this PATCH).
+        device=True returns the device tensor of nobjects x 208 characters, which is a later set's infos= as it is;
+        otherwise a list of (sha1_text, crc32_text) byte pairs, 200 and 8 characters, like checkpoint_texts().  A
+        digest the set does not keep marshals as zeros."""
+        torch, m = self.torch, self.nobjects
+        text = torch.empty(m * EFES_INFO_TEXT_BYTES, dtype=torch.uint8, device=self.device)
+        req = Infos(text=text.data_ptr() or None, sha1=self.states.data_ptr() if self.has_sha1 else None,
+                    crc32=self.crcs.data_ptr() if self.has_crc32 else None, n=m)
+        self._ordered(lambda stream: self.ctx.infos_marshal_text(req, stream))
+        if device:
+            return text
+        rows = text.cpu().numpy().reshape(m, EFES_INFO_TEXT_BYTES)
+        return [(bytes(r[:200]), bytes(r[200:])) for r in rows]
 
     @staticmethod
     def _check_order(order, build) -> None:
@@ -455,23 +558,27 @@ class DeviceObjects:
             raise ValueError('DeviceObjects: order= other than "table" needs build="device" (the host build emits table order)')
 
     def _build_on_device(self, data_ptr: int, ext, first, nchains, *, crcs, fresh, running, states, walk, copy_to,
-                         copy_offsets, checkpoints, order="table") -> None:
+                         copy_offsets, checkpoints, order="table", infos=None) -> None:
         """The rest of a set whose arrays efes_objects_jobs makes: ext, first (and copy_offsets) are device
         tensors, kept until the set goes; the states, sums, statuses and records as the host build allocates
         them; then the call on torch's current stream, with no wait behind it.  With an order other than
         "table": efes_objects_order (order="longest_first") and efes_objects_jobs_ordered instead, likewise."""
         torch, device, n, sha1 = self.torch, self.device, self.n, self.has_sha1
         self._table_ext, self._table_first, self._table_offsets = ext, first, copy_offsets
-        self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
-        assert self.init_crcs.size == self.nobjects
-        self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
+        if infos is not None:
+            self._resume_from_infos(infos)
+        else:
+            self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
+            assert self.init_crcs.size == self.nobjects
+            self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
         self.crcs = self._init_crcs_dev.clone() if self.nobjects else torch.zeros(4, dtype=torch.uint8, device=device)
         self.sums = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=device)
         self.status = torch.full((max(n, 1),), -99, dtype=torch.int32, device=device)
         if sha1:
-            self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
-            assert self.init_states.size == self.nobjects
-            self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
+            if infos is None:
+                self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
+                assert self.init_states.size == self.nobjects
+                self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
             self.states = self._init_states_dev.clone() if self.nobjects else torch.zeros(104, dtype=torch.uint8, device=device)
         self.running = bool(running)
         self.wide, self.walk = self._resolve_walk(walk, nchains)

@@ -13,6 +13,7 @@
 #include <new>
 #include <vector>
 
+#include "efes_infos_rules.hpp"
 #include "efes_internal.hpp"
 #include "efes_objects_rules.hpp"
 
@@ -564,6 +565,24 @@ int efes_checkpoints_marshal_text(efes_ctx* ctx, const efes_checkpoint* ckpt, ui
   if (!ckpt || !text) return EFES_ERR_ARG;
   DeviceGuard g(ctx->device);
   return hip_err(efes::launch_checkpoint_text(ckpt, n, text, pick(ctx, stream)));
+}
+
+int efes_infos_unmarshal_text(efes_ctx* ctx, const efes_infos* in, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::infos_check(in, true);
+  if (rc != EFES_OK) return rc;
+  if (in->n == 0 && !in->counts) return EFES_OK;  // nothing to launch
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_infos_unmarshal(*in, pick(ctx, stream)));
+}
+
+int efes_infos_marshal_text(efes_ctx* ctx, const efes_infos* in, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::infos_check(in, true);
+  if (rc != EFES_OK) return rc;
+  if (in->n == 0) return EFES_OK;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_infos_marshal(*in, pick(ctx, stream)));
 }
 
 int efes_crc32_tables(uint32_t* out, size_t nwords) {

@@ -205,6 +205,11 @@ hipError_t launch_objects_jobs_ordered(const efes_objects& in, const efes_object
                                        uint32_t* job_first, void* scratch, hipStream_t s);
 // The `.info` text of n checkpoints (efes_checkpoints_marshal_text): 208 characters per record.
 hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char* text, hipStream_t s);
+// Object infos (efes_infos_unmarshal_text, efes_infos_marshal_text; efes_infos.hip): 32 lanes per record, one text
+// word of 8 characters per lane; unmarshal clears counts in stream order first.  The arguments are checked by the
+// caller (infos_check, efes_infos_rules.hpp).
+hipError_t launch_infos_unmarshal(const efes_infos& in, hipStream_t s);
+hipError_t launch_infos_marshal(const efes_infos& in, hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

@@ -23,9 +23,9 @@ import threading
 
 import numpy as np
 
-from ._lib import MODE_AUTO, EfesError, Objects, ObjectsOut, PairStats, Plan, QueueStats, Results, Sha1State, check, lib
+from ._lib import MODE_AUTO, EfesError, Infos, Objects, ObjectsOut, PairStats, Plan, QueueStats, Results, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "objects_order_scratch", "objects_order_host", "objects_jobs_ordered_scratch", "objects_jobs_ordered_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "objects_order_scratch", "objects_order_host", "objects_jobs_ordered_scratch", "objects_jobs_ordered_host", "infos_unmarshal_text_host", "infos_marshal_text_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -128,6 +128,17 @@ def objects_jobs_ordered_host(table: Objects, out: ObjectsOut, order_ptr: int | 
     nobjects words of the order and the nobjects + 1 words of job_first (or None) are host addresses."""
     check(lib().efes_objects_jobs_ordered_host(ctypes.byref(table), ctypes.byref(out), order_ptr, job_first_ptr),
           "efes_objects_jobs_ordered_host")
+
+
+def infos_unmarshal_text_host(infos: Infos) -> None:
+    """efes_infos_unmarshal_text_host: Context.infos_unmarshal_text() on the host -- every array of `infos` is a host
+    address, the texts at any alignment.  Needs no GPU."""
+    check(lib().efes_infos_unmarshal_text_host(ctypes.byref(infos)), "efes_infos_unmarshal_text_host")
+
+
+def infos_marshal_text_host(infos: Infos) -> None:
+    """efes_infos_marshal_text_host: Context.infos_marshal_text() on the host.  Needs no GPU."""
+    check(lib().efes_infos_marshal_text_host(ctypes.byref(infos)), "efes_infos_marshal_text_host")
 
 
 class Context:
@@ -272,6 +283,18 @@ class Context:
         MarshalText, then the 8 of the CRC's (asynchronous on `stream`)."""
         check(lib().efes_checkpoints_marshal_text(self.handle, ckpt_ptr, n, text_ptr, stream),
               "efes_checkpoints_marshal_text")
+
+    def infos_unmarshal_text(self, infos: Infos, stream: int | None = None) -> None:
+        """efes_infos_unmarshal_text: the n `.info` records at infos.text (208 characters each, device memory)
+        decoded into the states at infos.sha1 and infos.crc32; a record with a character that is no hex digit leaves
+        the refusing state (nx = EFES_SHA1_NX_REFUSED), CRC 0 and status EFES_ERR_INVALID_DIGEST, and is counted in
+        infos.counts[1].  Asynchronous on `stream`, so the builder and a walk queue directly behind it."""
+        check(lib().efes_infos_unmarshal_text(self.handle, ctypes.byref(infos), stream), "efes_infos_unmarshal_text")
+
+    def infos_marshal_text(self, infos: Infos, stream: int | None = None) -> None:
+        """efes_infos_marshal_text: the states at infos.sha1 and infos.crc32 (zeros for one that is None) encoded
+        into n `.info` records at infos.text, 208 lower-case characters each (asynchronous on `stream`)."""
+        check(lib().efes_infos_marshal_text(self.handle, ctypes.byref(infos), stream), "efes_infos_marshal_text")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

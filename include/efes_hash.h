@@ -671,7 +671,8 @@ typedef struct efes_checkpoint {
  * ckpt[i].sha1 and then the 8 that efes_crc32_state_marshal_text gives for ckpt[i].crc32; no NUL, nothing
  * behind n * 208 characters is written.  Asynchronous on `stream`; n <= EFES_HASH_CHAIN_MAX_JOBS.
  * EFES_ERR_ARG for a NULL ctx, a larger n, or a NULL pointer with n > 0; n == 0 returns EFES_OK and
- * launches nothing.  Unmarshalling stays on the host (efes_sha1_state_unmarshal_text below). */
+ * launches nothing.  The per-object states of an object table go from and to such texts on the device through
+ * efes_infos_unmarshal_text and efes_infos_marshal_text ("Object infos", below). */
 int efes_hash_chain_checkpoints(efes_ctx* ctx, const efes_job* jobs_device, uint32_t njobs,
                                 efes_checkpoint* const* ckpt_device, void* scratch_device, size_t scratch_bytes,
                                 void* stream, int mode);
@@ -1096,6 +1097,99 @@ int efes_objects_jobs_ordered(efes_ctx* ctx, const efes_objects* in, const efes_
                               size_t scratch_bytes, void* stream);
 int efes_objects_jobs_ordered_host(const efes_objects* in, const efes_objects_out* out, const uint32_t* order,
                                    uint32_t* job_first);
+
+/* Object infos: the per-object states of an object table FROM and TO their `.info` texts, ON THE DEVICE.  A PATCH
+ * that is not an upload's first resumes both digests from the texts in `<path>.info` (filereceiver.go:182-188,
+ * fileinfo.go:29-45, sha1_efes.go:40-64, crc32_efes.go:26-40) and writes the new texts back behind it
+ * (filereceiver.go:226, fileinfo.go:47-58).  For an object table those are efes_infos_unmarshal_text in front of
+ * efes_objects_jobs and efes_infos_marshal_text behind efes_objects_results: texts -> states -> builder -> walk ->
+ * results -> texts is one chain of stream-ordered calls with no host synchronisation in it.
+ *
+ * efes_infos is a HOST struct; the pointers in it are device addresses (host addresses for the _host twins).
+ * Record i is the EFES_INFO_TEXT_BYTES characters at text + 208 i: the 200 of the SHA-1 state's MarshalText
+ * (sha1_efes.go:25-38), then the 8 of the CRC's (crc32_efes.go:18-24), no NUL -- the layout of
+ * efes_checkpoints_marshal_text.  A length error cannot arise from this layout: a caller whose text for an object
+ * has another length (Go: errInvalidDigest) fills that record with a character that is no hex digit.
+ *
+ * efes_infos_unmarshal_text, per record i.  The text is VALID when all 208 characters are hex digits as Go's
+ * encoding/hex accepts them (0-9, a-f, A-F); all 208 are checked even when sha1 or crc32 is NULL, because an `.info`
+ * record always holds both.
+ *   - valid: sha1[i] holds exactly what efes_sha1_state_unmarshal_text gives for characters 0..199, and _pad is
+ *     written as 0; nx is stored as decoded, whatever its value, as Go does on a 64-bit int; crc32[i].crc is the
+ *     big-endian decode of characters 200..207; status[i] = EFES_OK;
+ *   - invalid: sha1[i] becomes the REFUSING STATE -- every byte 0 except nx = EFES_SHA1_NX_REFUSED --,
+ *     crc32[i].crc = 0, status[i] = EFES_ERR_INVALID_DIGEST.  Go fails that one upload (errInvalidDigest -> 500) and
+ *     hashes nothing for it; the refusing state does the same for an object of a table, and uses only what the job
+ *     and chain kernels already promise for nx > 64 (sha1.go:62): every Write into it gets EFES_ERR_STATE and writes
+ *     nothing, the members behind it get the same, nothing is gathered and no record is stored, and
+ *     efes_objects_results reports EFES_VERDICT_FAILED.  The other objects of the table run;
+ *   - a CRC-ONLY table (sha1 == NULL) has no such state: the CRC of an invalid text is 0, which hashes like any
+ *     other start.  Such a caller reads counts[1] or status before it trusts the CRCs;
+ *   - every word of every state of [0, n) is written by every call, so nothing stale survives; nothing outside the
+ *     named arrays is written;
+ *   - counts (may be NULL) is written whole: counts[0] = valid texts, counts[1] = invalid ones, {0, 0} for n == 0.
+ * efes_infos_marshal_text, per record i: characters 0..199 are those of efes_sha1_state_marshal_text(&sha1[i]), or
+ * 200 x '0' when sha1 == NULL -- what a checkpoint record holds for a chain without SHA-1 --, characters 200..207
+ * those of efes_crc32_state_marshal_text(&crc32[i]), or 8 x '0'.  Lower-case hex, no NUL, nothing behind 208 n is
+ * written; status and counts are ignored.  A pure codec: a refusing state marshals like any other, and _pad is not
+ * read.
+ * Both calls are asynchronous on `stream` (NULL = the context stream) and need no scratch, host read-back,
+ * allocation or wait; their outputs are visible to later work in stream order, so efes_objects_jobs and a walk queue
+ * directly behind an unmarshal.  The caller's contract, not checked: the arrays overlap neither each other nor
+ * anything else in use.
+ * Errors, checked first and without the device: EFES_ERR_ARG for a NULL ctx (device calls) or in, n >
+ * EFES_OBJECTS_MAX, a nonzero _reserved; with n > 0 a NULL text, or sha1 and crc32 both NULL; sha1 not 8-byte
+ * aligned; crc32, status or counts not 4-byte aligned; and, on the device calls only, text not 8-byte aligned.  A
+ * refused call writes nothing.  n == 0 returns EFES_OK; unmarshal still writes counts when given, and nothing else
+ * is launched.
+ * 32 lanes per record, one text word of 8 characters (one 64-bit load or store) and one 32-bit state word per lane;
+ * the verdict of a record is a ballot masked to its half of the wavefront, and the lanes store either the decoded
+ * word or the refusing image's at the same place; counts start at {n, 0} in stream order, and only a workgroup
+ * that holds invalid records moves their number over with two vector atomics.  Every grid is sized from n
+ * (DESIGN.md §4 "Object infos").
+ *
+ * The two _host twins are the same functions over HOST arrays, with no context and no stream; they take text at any
+ * alignment.  For a caller whose texts or states are on the host anyway, and for checking the rules on a machine
+ * without a GPU.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/infos/bench.json, tools/bench_infos.py; DESIGN.md §4 "Object infos" has the
+ * table; 4096, 32 768, 65 536, 262 144 and 1 048 576 records of random states, 1 % of the texts spoiled; wall-clock,
+ * nine repetitions, a path wins where its median is below the other's minimum; "device path" = the texts from host
+ * memory to the device, the call, a synchronise; "host path" = the host twin, the states and CRCs to the device
+ * (108 bytes per object), a synchronise; for marshal the mirror image, call + 208 n bytes to the host against 108 n
+ * bytes to the host + the twin):
+ *   - unmarshal, on all five counts: the DEVICE path, at 0.11, 0.047, 0.038, 0.032 and 0.031 of the host path's
+ *     time -- 0.064 ms against 0.59, 0.21 against 4.4, 0.33 against 8.8, 1.10 against 35.1 and 4.4 ms against 146.7
+ *     -- although it uploads 208 bytes per object where the host path uploads 108: the twin's decode is what the
+ *     host path spends;
+ *   - marshal, on all five counts: the DEVICE path, at 0.15, 0.048, 0.044, 0.040 and 0.039 of the host path's time
+ *     (0.070 ms against 0.46 up to 4.1 ms against 109.8);
+ *   - what the library offered before, efes_sha1_state_unmarshal_text and efes_crc32_state_unmarshal_text per object
+ *     through the Python binding, then the same upload: 11.2, 90.0 and 184.8 ms at 4096, 32 768 and 65 536 records
+ *     (not timed beyond), 175 to 560 times the device path;
+ *   - the calls alone, device time: unmarshal 10, 16, 23, 64 and 224 us, marshal 6, 7, 11, 30 and 136 us.  Up to
+ *     65 536 records that is launches, as expected; beyond it is bytes: 1.3 to 1.5 TB/s read plus written for
+ *     unmarshal, 2.4 to 2.8 for marshal, of the 8 TB/s HBM peak;
+ *   - the counters were NOT free as first built (every workgroup adding both sums: profiles/infos/
+ *     bench_every_workgroup_adds.json): 131 072 workgroups' atomics on two words made the unmarshal call 1.61 ms at
+ *     1 048 576 records and 0.41 ms at 262 144, six to seven times what it takes now.  Now only a workgroup with an invalid
+ *     text touches them; with EVERY text invalid the call takes 12, 33, 56, 197 and 760 us. */
+#define EFES_INFO_TEXT_BYTES EFES_CHECKPOINT_TEXT_BYTES /* 208: 200 (sha1_efes.go:25-38) + 8 (crc32_efes.go:18-24), no NUL */
+#define EFES_SHA1_NX_REFUSED 65                         /* nx of the refusing state: the smallest nx a Write refuses */
+
+typedef struct efes_infos {     /* a HOST struct; the pointers are device addresses (host addresses for the _host twins) */
+    char*             text;     /* 208 * n characters; record i at text + 208 i */
+    efes_sha1_state*  sha1;     /* n states, or NULL */
+    efes_crc32_state* crc32;    /* n states, or NULL */
+    int32_t*          status;   /* n words, or NULL; written by unmarshal only */
+    uint32_t*         counts;   /* 2 words, or NULL; written by unmarshal only: [0] valid texts, [1] invalid */
+    uint32_t n, _reserved;      /* _reserved 0 */
+} efes_infos;                   /* 48 bytes */
+
+int efes_infos_unmarshal_text(efes_ctx* ctx, const efes_infos* in, void* stream);
+int efes_infos_marshal_text(efes_ctx* ctx, const efes_infos* in, void* stream);
+int efes_infos_unmarshal_text_host(const efes_infos* in);
+int efes_infos_marshal_text_host(const efes_infos* in);
 
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
