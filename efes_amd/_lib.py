@@ -148,6 +148,42 @@ EFES_INFO_TEXT_BYTES = 208  # 200 characters of the SHA-1 state's MarshalText, t
 EFES_SHA1_NX_REFUSED = 65   # nx of the refusing state an invalid text leaves: every Write into it gets EFES_ERR_STATE
 assert ctypes.sizeof(Infos) == 48
 
+
+class Patch(ctypes.Structure):
+    """efes_patch: one PATCH request of an arrival log (efes_patches_table)."""
+    _fields_ = [("data_offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("file_offset", ctypes.c_uint64),
+                ("file_length", ctypes.c_uint64), ("object", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
+class PatchAnswer(ctypes.Structure):
+    """efes_patch_answer: what one PATCH is answered with, and its slot in the table."""
+    _fields_ = [("offset", ctypes.c_uint64), ("verdict", ctypes.c_uint32), ("slot", ctypes.c_uint32)]
+
+
+class PatchObject(ctypes.Structure):
+    """efes_patch_object: one upload after the log."""
+    _fields_ = [("offset", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("admitted", ctypes.c_uint32)]
+
+
+class Patches(ctypes.Structure):
+    """efes_patches: an arrival log of PATCH requests and where its object table goes; a host struct of device
+    addresses (host ones for efes_patches_table_host)."""
+    _fields_ = [("log", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("sha1", ctypes.c_void_p), ("crc32", ctypes.c_void_p),
+                ("extents", ctypes.c_void_p), ("first", ctypes.c_void_p), ("answers", ctypes.c_void_p), ("objects", ctypes.c_void_p),
+                ("patch_of", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("nobjects", ctypes.c_uint32), ("npatches", ctypes.c_uint32)]
+
+
+EFES_PATCH_ADMITTED, EFES_PATCH_CONFLICT, EFES_PATCH_DEFERRED, EFES_PATCH_DONE, EFES_PATCH_INVALID = 0, 1, 2, 3, 4
+EFES_PATCH_OBJ_RESTARTED, EFES_PATCH_OBJ_DONE, EFES_PATCH_OBJ_DEFERRED = 0x1, 0x2, 0x4
+EFES_PATCH_LENGTH_UNKNOWN = (1 << 64) - 1  # no efes-file-length header: Go's -1
+PATCH_LANE = 64  # kPatchLane of efes_patches.hip: the longest segment one lane walks (the admission's seam)
+PATCH_DTYPE = np.dtype([("data_offset", "<u8"), ("length", "<u8"), ("file_offset", "<u8"), ("file_length", "<u8"),
+                        ("object", "<u4"), ("_reserved", "<u4")])
+PATCH_ANSWER_DTYPE = np.dtype([("offset", "<u8"), ("verdict", "<u4"), ("slot", "<u4")])
+PATCH_OBJECT_DTYPE = np.dtype([("offset", "<u8"), ("flags", "<u4"), ("admitted", "<u4")])
+assert ctypes.sizeof(Patch) == 40 == PATCH_DTYPE.itemsize and ctypes.sizeof(PatchAnswer) == 16 == PATCH_ANSWER_DTYPE.itemsize
+assert ctypes.sizeof(PatchObject) == 16 == PATCH_OBJECT_DTYPE.itemsize and ctypes.sizeof(Patches) == 88
+
 assert ctypes.sizeof(Sha1State) == 104 and ctypes.sizeof(Job) == 56 and ctypes.sizeof(QueueStats) == 32
 assert ctypes.sizeof(PairStats) == 32
 
@@ -264,6 +300,9 @@ SIGNATURES = {
     "efes_infos_marshal_text": (_I, [_VP, _P(Infos), _VP]),
     "efes_infos_unmarshal_text_host": (_I, [_P(Infos)]),
     "efes_infos_marshal_text_host": (_I, [_P(Infos)]),
+    "efes_patches_table_scratch": (_S, [_U32, _U32]),
+    "efes_patches_table": (_I, [_VP, _P(Patches), _VP, _S, _VP]),
+    "efes_patches_table_host": (_I, [_P(Patches)]),
     "efes_sha1_state_marshal_text": (None, [_P(Sha1State), _VP]),
     "efes_sha1_state_unmarshal_text": (_I, [_P(Sha1State), ctypes.c_char_p, _S]),
     "efes_crc32_state_marshal_text": (None, [_P(Crc32State), _VP]),

@@ -10,8 +10,9 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import (CHECKPOINT_DTYPE, CHECKPOINT_TEXT_BYTES, EFES_HASH_CRC32, EFES_HASH_SHA1, EFES_INFO_TEXT_BYTES, EFES_OBJECTS_FRESH, EFES_OBJECTS_RUNNING, EFES_JOB_CHAIN, EFES_JOB_FINALIZE, EFES_JOB_INIT, EFES_JOB_SUM_ONLY, JOB_DTYPE, MODE_AUTO, MODE_DEEP, MODE_FED4,
-                   MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Infos, Objects, ObjectsOut, Plan, PlanPart, Results)
-from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_ordered_scratch, objects_jobs_scratch, objects_order_scratch, objects_results_scratch
+                   MODE_FED4E, MODE_GROUP, MODE_WIDE, OBJECT_RESULT_DTYPE, PATCH_ANSWER_DTYPE, PATCH_DTYPE, PATCH_OBJECT_DTYPE, PLAN_MAX_PARTS, SHA1_STATE_DTYPE, Infos, Objects, ObjectsOut, Patches, Plan, PlanPart,
+                   Results)
+from .hashing import Context, crc32_batch_scratch, crc32_chain_scratch, crc32_copy_scratch, default_context, hash_chain_auto_mode, hash_chain_auto_mode_wide, hash_chain_scratch, objects_jobs_ordered_scratch, objects_jobs_scratch, objects_order_scratch, objects_results_scratch, patches_table_scratch
 
 MODE_PLAN = -1  # run(): efes_plan_batch + efes_hash_submit_plan instead of one fixed kernel shape
 
@@ -461,6 +462,117 @@ class DeviceObjects:
                               infos=infos)
         return self
 
+    @classmethod
+    def from_patches(cls, data_ptr: int, log, offsets=None, *, nobjects: int | None = None, infos=None,
+                     states: np.ndarray | None = None, crcs: np.ndarray | None = None, sha1: bool = False, crc32: bool = True,
+                     walk=None, running: bool = False, checkpoints: bool = False, copy_to: int | None = None, order="table",
+                     ctx: Context | None = None, device: str = "cuda:0") -> "DeviceObjects":
+        """The set of an ARRIVAL LOG of PATCH requests: `log`, a host PATCH_DTYPE array or a device tensor of
+        npatches x 40 bytes, in arrival order and interleaved over the uploads as a server receives them, and
+        `offsets`, the FileInfo.Offset every upload has before the log (a host array or a device tensor of nobjects
+        64-bit integers; None: all 0).  efes_patches_table sorts the log by upload and applies saveFile's rules on
+        torch's current stream -- behind the initial states (states=, crcs= or infos=, as for the constructor;
+        without them NewSha1() and CRC 0) and in front of the builder, with no wait anywhere -- so the set is the
+        table of the ADMITTED PATCHes: one slot per PATCH, a refused one of length 0.  The uploads never start
+        fresh: each resumes from its state, which the call re-initialises for an upload that a PATCH at offset 0
+        restarts; reset() restores the states with those restarts applied.  nobjects is taken from offsets, infos,
+        states or crcs, whichever is given, else it must be passed.  walk="auto" and "auto_wide" raise as for
+        from_table().  patch_answers_host() is what every PATCH is answered with (verdict, efes-file-offset and
+        slot, in arrival order), patch_objects_host() every upload's new offset, flags and admitted count,
+        patch_counts() the PATCHes per verdict and patch_of_host() the arrival index of every slot.  With
+        running=True the digests of a DONE PATCH are running_sha1()[slot] and running_crcs()[slot] of its answer's slot."""
+        if hasattr(log, "data_ptr"):
+            if log.element_size() * int(log.numel()) % PATCH_DTYPE.itemsize or not log.is_contiguous():
+                raise ValueError("DeviceObjects.from_patches: log is a contiguous device tensor of npatches x 40 bytes")
+            npatches = log.element_size() * int(log.numel()) // PATCH_DTYPE.itemsize
+        else:
+            log = np.ascontiguousarray(log)
+            if log.dtype != PATCH_DTYPE or log.ndim != 1:
+                raise ValueError("DeviceObjects.from_patches: log is a one-dimensional PATCH_DTYPE array (or a device tensor)")
+            npatches = int(log.size)
+        for given in (offsets, states, crcs):
+            if nobjects is None and given is not None:
+                nobjects = int(given.numel()) if hasattr(given, "data_ptr") else int(np.asarray(given).shape[0])
+        if nobjects is None and infos is not None:
+            nobjects = int(infos.numel()) // EFES_INFO_TEXT_BYTES if hasattr(infos, "data_ptr") else len(infos)
+        if nobjects is None:
+            raise ValueError("DeviceObjects.from_patches: nobjects= (or offsets=, infos=, states= or crcs=, which give it)")
+        if offsets is not None and (int(offsets.numel()) if hasattr(offsets, "data_ptr") else int(np.asarray(offsets).size)) != nobjects:
+            raise ValueError(f"DeviceObjects.from_patches: offsets has not {nobjects} entries")
+        DeviceObjects._check_order(order, "device")
+        if checkpoints and not sha1:
+            raise ValueError("DeviceObjects: checkpoints= needs sha1=True (a CRC-only set's running CRCs are its checkpoints)")
+        if copy_to is not None and sha1 and not (isinstance(walk, str) and walk == "wide"):
+            raise ValueError('DeviceObjects: copy_to= with sha1=True needs walk="wide" (efes_hash_chain_wide_copy)')
+        if not (sha1 or crc32):
+            raise ValueError("DeviceObjects: sha1 or crc32 (or both)")
+        if (walk is not None or states is not None) and not sha1:
+            raise ValueError("DeviceObjects: walk= and states= need sha1=True")
+        if isinstance(walk, str) and walk in ("auto", "auto_wide"):
+            raise ValueError(f'DeviceObjects.from_patches: walk={walk!r} needs the chain count on the host')
+        _, infos = DeviceObjects._check_infos(infos, False, states, crcs, nobjects)
+        import torch
+
+        self = cls.__new__(cls)
+        self.has_sha1, self.has_crc32 = bool(sha1), bool(crc32)
+        self.build = "device"
+        self.ctx = ctx or default_context(int(device.split(":")[1]) if ":" in device else 0)
+        self.torch = torch
+        self.device = device
+        m, n = int(nobjects), int(npatches)
+        self.nobjects, self.n = m, n
+        self._patch_log = log if hasattr(log, "data_ptr") else torch.from_numpy(log.view(np.uint8).reshape(-1)).to(device)
+        if offsets is None or hasattr(offsets, "data_ptr"):
+            self._patch_offsets = offsets
+        else:
+            self._patch_offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to(device)
+        ext = torch.empty((n, 2), dtype=torch.int64, device=device)
+        first = torch.empty(m + 1, dtype=torch.int32, device=device)
+        self._patch_answers = torch.empty(max(n, 1) * PATCH_ANSWER_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self._patch_objects = torch.empty(max(m, 1) * PATCH_OBJECT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self._patch_of = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        self._patch_counts = torch.empty(5, dtype=torch.int32, device=device)
+        self._patch_scratch = torch.empty(patches_table_scratch(m, n), dtype=torch.uint8, device=device)
+
+        def table():  # behind the initial states, in front of their clones
+            req = Patches(log=self._patch_log.data_ptr() or None,
+                          offsets=None if self._patch_offsets is None else (self._patch_offsets.data_ptr() or None),
+                          sha1=(self._init_states_dev.data_ptr() or None) if sha1 else None,
+                          crc32=(self._init_crcs_dev.data_ptr() or None) if crc32 else None,
+                          extents=ext.data_ptr() or None, first=first.data_ptr(), answers=self._patch_answers.data_ptr(),
+                          objects=self._patch_objects.data_ptr(), patch_of=self._patch_of.data_ptr(),
+                          counts=self._patch_counts.data_ptr(), nobjects=m, npatches=n)
+            self._ordered(lambda stream: self.ctx.patches_table(req, self._patch_scratch.data_ptr(), self._patch_scratch.numel(), stream))
+
+        self._build_on_device(data_ptr, ext, first, None, crcs=crcs, fresh=False, running=running, states=states, walk=walk,
+                              copy_to=copy_to, copy_offsets=None, checkpoints=checkpoints, order=order, infos=infos,
+                              before_clone=table)
+        return self
+
+    def _need_patches(self, what: str) -> None:
+        if "_patch_counts" not in self.__dict__:
+            raise ValueError(f"{what}: build the set with from_patches()")
+
+    def patch_answers_host(self) -> np.ndarray:
+        """Per PATCH, in arrival order: a PATCH_ANSWER_DTYPE array of (offset, verdict, slot)."""
+        self._need_patches("patch_answers_host")
+        return self._patch_answers.cpu().numpy()[: self.n * PATCH_ANSWER_DTYPE.itemsize].view(PATCH_ANSWER_DTYPE).copy()
+
+    def patch_objects_host(self) -> np.ndarray:
+        """Per upload: a PATCH_OBJECT_DTYPE array of (offset after the log, EFES_PATCH_OBJ_* flags, admitted PATCHes)."""
+        self._need_patches("patch_objects_host")
+        return self._patch_objects.cpu().numpy()[: self.nobjects * PATCH_OBJECT_DTYPE.itemsize].view(PATCH_OBJECT_DTYPE).copy()
+
+    def patch_counts(self) -> tuple:
+        """(admitted, conflict, deferred, done, invalid): the PATCHes per verdict (20 bytes read back)."""
+        self._need_patches("patch_counts")
+        return tuple(int(c) for c in self._patch_counts.cpu().numpy().view(np.uint32))
+
+    def patch_of_host(self) -> np.ndarray:
+        """Per slot of the table: the arrival index of its PATCH."""
+        self._need_patches("patch_of_host")
+        return self._patch_of.cpu().numpy().view(np.uint32)[: self.n].copy()
+
     @staticmethod
     def _check_infos(infos, fresh, states, crcs, nobjects: int):
         """(fresh, infos) of the infos= and fresh= arguments, checked from the arguments alone: no device is touched.
@@ -558,11 +670,13 @@ class DeviceObjects:
             raise ValueError('DeviceObjects: order= other than "table" needs build="device" (the host build emits table order)')
 
     def _build_on_device(self, data_ptr: int, ext, first, nchains, *, crcs, fresh, running, states, walk, copy_to,
-                         copy_offsets, checkpoints, order="table", infos=None) -> None:
+                         copy_offsets, checkpoints, order="table", infos=None, before_clone=None) -> None:
         """The rest of a set whose arrays efes_objects_jobs makes: ext, first (and copy_offsets) are device
         tensors, kept until the set goes; the states, sums, statuses and records as the host build allocates
         them; then the call on torch's current stream, with no wait behind it.  With an order other than
-        "table": efes_objects_order (order="longest_first") and efes_objects_jobs_ordered instead, likewise."""
+        "table": efes_objects_order (order="longest_first") and efes_objects_jobs_ordered instead, likewise.
+        before_clone, where given, is called once the initial states lie on the device (_init_crcs_dev,
+        _init_states_dev) and before they are cloned into the working states: what it queues there reaches both."""
         torch, device, n, sha1 = self.torch, self.device, self.n, self.has_sha1
         self._table_ext, self._table_first, self._table_offsets = ext, first, copy_offsets
         if infos is not None:
@@ -571,14 +685,16 @@ class DeviceObjects:
             self.init_crcs = np.zeros(self.nobjects, np.uint32) if crcs is None else np.asarray(crcs, dtype=np.uint32)
             assert self.init_crcs.size == self.nobjects
             self._init_crcs_dev = torch.from_numpy(self.init_crcs.view(np.uint8).copy()).to(device)
+            if sha1:
+                self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
+                assert self.init_states.size == self.nobjects
+                self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
+        if before_clone is not None:
+            before_clone()
         self.crcs = self._init_crcs_dev.clone() if self.nobjects else torch.zeros(4, dtype=torch.uint8, device=device)
         self.sums = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=device)
         self.status = torch.full((max(n, 1),), -99, dtype=torch.int32, device=device)
         if sha1:
-            if infos is None:
-                self.init_states = fresh_states(self.nobjects) if states is None else np.array(states, dtype=SHA1_STATE_DTYPE)
-                assert self.init_states.size == self.nobjects
-                self._init_states_dev = torch.from_numpy(self.init_states.view(np.uint8).copy()).to(device)
             self.states = self._init_states_dev.clone() if self.nobjects else torch.zeros(104, dtype=torch.uint8, device=device)
         self.running = bool(running)
         self.wide, self.walk = self._resolve_walk(walk, nchains)

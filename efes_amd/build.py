@@ -13,10 +13,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libefeshash.so")
-SOURCES = ["efes_kernels.hip", "efes_chain_wide.hip", "efes_chain_wide_copy.hip", "efes_objects.hip", "efes_objects_results.hip", "efes_objects_order.hip", "efes_infos.hip", "efes_crc_span.hip", "efes_crc_batch.hip", "efes_api.cpp", "efes_ingest.cpp", "efes_queue.cpp",
-           "efes_stream.cpp", "efes_plan.cpp", "efes_objects.cpp", "efes_infos.cpp"]
+SOURCES = ["efes_kernels.hip", "efes_chain_wide.hip", "efes_chain_wide_copy.hip", "efes_objects.hip", "efes_objects_results.hip", "efes_objects_order.hip", "efes_infos.hip", "efes_patches.hip", "efes_crc_span.hip", "efes_crc_batch.hip", "efes_api.cpp", "efes_ingest.cpp", "efes_queue.cpp",
+           "efes_stream.cpp", "efes_plan.cpp", "efes_objects.cpp", "efes_infos.cpp", "efes_patches.cpp"]
 HEADERS = ["efes_internal.hpp", "efes_gf2.hpp", "sha1_device.hpp", "efes_wide_device.hpp", "efes_chain_wide_device.hpp",
-           "efes_chain_wide_body.inc", "efes_objects_rules.hpp", "efes_infos_rules.hpp"]
+           "efes_chain_wide_body.inc", "efes_objects_rules.hpp", "efes_infos_rules.hpp", "efes_patches_rules.hpp"]
 PUBLIC_HEADERS = ["efes_hash.h", "efes_testing.h"]
 ARCH = "gfx950"
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "efes_infos_rules.hpp"
+#include "efes_patches_rules.hpp"
 #include "efes_internal.hpp"
 #include "efes_objects_rules.hpp"
 
@@ -583,6 +584,21 @@ int efes_infos_marshal_text(efes_ctx* ctx, const efes_infos* in, void* stream) {
   if (in->n == 0) return EFES_OK;
   DeviceGuard g(ctx->device);
   return hip_err(efes::launch_infos_marshal(*in, pick(ctx, stream)));
+}
+
+size_t efes_patches_table_scratch(uint32_t nobjects, uint32_t npatches) {
+  return efes::patches_table_scratch_bytes(nobjects, npatches);
+}
+
+int efes_patches_table(efes_ctx* ctx, const efes_patches* in, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!ctx) return EFES_ERR_ARG;
+  const int rc = efes::patches_check(in);
+  if (rc != EFES_OK) return rc;
+  if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+      scratch_bytes < efes::patches_table_scratch_bytes(in->nobjects, in->npatches))
+    return EFES_ERR_ARG;
+  DeviceGuard g(ctx->device);
+  return hip_err(efes::launch_patches_table(*in, scratch, pick(ctx, stream)));
 }
 
 int efes_crc32_tables(uint32_t* out, size_t nwords) {

@@ -210,6 +210,11 @@ hipError_t launch_checkpoint_text(const efes_checkpoint* ckpt, uint32_t n, char*
 // caller (infos_check, efes_infos_rules.hpp).
 hipError_t launch_infos_unmarshal(const efes_infos& in, hipStream_t s);
 hipError_t launch_infos_marshal(const efes_infos& in, hipStream_t s);
+// PATCH logs (efes_patches_table; efes_patches.hip): a stable radix sort of (object, arrival index) whose number of
+// digit passes is fixed from nobjects, first[] by lower bounds, then the admission pass, one lane per object or one
+// wavefront per long segment.  The arguments are checked by the caller (patches_check, efes_patches_rules.hpp).
+size_t patches_table_scratch_bytes(uint32_t nobjects, uint32_t npatches);
+hipError_t launch_patches_table(const efes_patches& in, void* scratch, hipStream_t s);
 
 // Lanes per job of a grouped-DEEP mode (EFES_MODE_GROUPn -> n), 0 for other modes.
 inline int group_of_mode(int mode) {

@@ -23,9 +23,9 @@ import threading
 
 import numpy as np
 
-from ._lib import MODE_AUTO, EfesError, Infos, Objects, ObjectsOut, PairStats, Plan, QueueStats, Results, Sha1State, check, lib
+from ._lib import MODE_AUTO, EfesError, Infos, Objects, ObjectsOut, PairStats, Patches, Plan, QueueStats, Results, Sha1State, check, lib
 
-__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "objects_order_scratch", "objects_order_host", "objects_jobs_ordered_scratch", "objects_jobs_ordered_host", "infos_unmarshal_text_host", "infos_marshal_text_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
+__all__ = ["Context", "default_context", "device_count", "open_devices", "crc32_combine", "crc32_batch_scratch", "crc32_chain_scratch", "crc32_copy_scratch", "hash_chain_scratch", "hash_chain_auto_mode", "hash_chain_auto_mode_wide", "objects_jobs_scratch", "objects_jobs_host", "objects_results_scratch", "objects_results_host", "objects_order_scratch", "objects_order_host", "objects_jobs_ordered_scratch", "objects_jobs_ordered_host", "infos_unmarshal_text_host", "infos_marshal_text_host", "patches_table_scratch", "patches_table_host", "Sha1Digest", "CRC32Digest", "Sha1File", "Digest", "FileInfo",
            "new_sha1", "new_crc32_ieee", "EfesError"]
 
 
@@ -139,6 +139,17 @@ def infos_unmarshal_text_host(infos: Infos) -> None:
 def infos_marshal_text_host(infos: Infos) -> None:
     """efes_infos_marshal_text_host: Context.infos_marshal_text() on the host.  Needs no GPU."""
     check(lib().efes_infos_marshal_text_host(ctypes.byref(infos)), "efes_infos_marshal_text_host")
+
+
+def patches_table_scratch(nobjects: int, npatches: int) -> int:
+    """efes_patches_table_scratch: scratch bytes Context.patches_table needs (never 0; 0 above EFES_OBJECTS_MAX)."""
+    return int(lib().efes_patches_table_scratch(nobjects, npatches))
+
+
+def patches_table_host(patches: Patches) -> None:
+    """efes_patches_table_host: Context.patches_table() on the host -- every array of `patches` is a host address.
+    Needs no GPU."""
+    check(lib().efes_patches_table_host(ctypes.byref(patches)), "efes_patches_table_host")
 
 
 class Context:
@@ -295,6 +306,13 @@ class Context:
         """efes_infos_marshal_text: the states at infos.sha1 and infos.crc32 (zeros for one that is None) encoded
         into n `.info` records at infos.text, 208 lower-case characters each (asynchronous on `stream`)."""
         check(lib().efes_infos_marshal_text(self.handle, ctypes.byref(infos), stream), "efes_infos_marshal_text")
+
+    def patches_table(self, patches: Patches, scratch_ptr: int | None, scratch_bytes: int, stream: int | None = None) -> None:
+        """efes_patches_table: the arrival log of PATCH records at patches.log sorted by upload and run through
+        saveFile's admission rules on the device: the object table (extents, first) that objects_jobs takes as it
+        is, the answer of every PATCH, the new offset of every upload, and fresh states for restarted uploads.
+        Asynchronous on `stream`, so the builder and a walk queue directly behind it."""
+        check(lib().efes_patches_table(self.handle, ctypes.byref(patches), scratch_ptr, scratch_bytes, stream), "efes_patches_table")
 
     def debug_fault_after(self, k: int) -> None:
         """Test hook (efes_debug_fault_after): the k-th launch of this context's digest queue faults."""

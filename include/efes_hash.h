@@ -1191,6 +1191,120 @@ int efes_infos_marshal_text(efes_ctx* ctx, const efes_infos* in, void* stream);
 int efes_infos_unmarshal_text_host(const efes_infos* in);
 int efes_infos_marshal_text_host(const efes_infos* in);
 
+/* PATCH logs: the object table of an arrival log of PATCH requests, made ON THE DEVICE.  Every call of the object
+ * pipeline takes a finished table -- extents[] grouped by object and in byte order, plus first[] -- but a storage
+ * server receives PATCH requests in arrival order, interleaved over its uploads, and saveFile (filereceiver.go:171-227)
+ * decides what becomes of each before a byte is hashed.  efes_patches_table applies those rules per upload, in arrival
+ * order, and writes the table efes_objects_jobs takes as it is, the answer every request gets and the new
+ * FileInfo.Offset of every upload: log -> table -> builder -> walk is one chain of stream-ordered calls.
+ *
+ * efes_patches is a HOST struct; the pointers in it are device addresses (host addresses for the _host twin).
+ * The rules, per object i = p.object in arrival order, arithmetic modulo 2^64 (cur starts at offsets[i], or 0):
+ *   - p.object >= nobjects: EFES_PATCH_INVALID, answer offset 0; no upload is touched;
+ *   - the object is closed (below): EFES_PATCH_DEFERRED, answer offset cur;
+ *   - p.file_offset == 0 (filereceiver.go:174-180, a restart with fresh digests): if a PATCH of i was already
+ *     admitted in this log the object closes and the PATCH is DEFERRED; otherwise i is RESTARTED, cur = p.length;
+ *   - else p.file_offset == cur: cur += p.length;
+ *   - else EFES_PATCH_CONFLICT (409, :186-187), answer offset cur, the required offset;
+ *   - an admitted PATCH with cur == p.file_length (:219-224) is EFES_PATCH_DONE and closes the object; any other is
+ *     EFES_PATCH_ADMITTED (:226).  Both answer with the new cur.
+ * DEFERRED is the one verdict that is no Go answer.  One table holds one chain per object, so a restart behind
+ * admitted bytes and anything behind a DONE wait: they come back untouched and in order, and resubmitting them in
+ * the next log with the offsets updated (0 and fresh states after a DONE, as Go's deleted `.info` gives) yields what
+ * Go's sequential handling yields.
+ * The table: the slots are the log stably sorted by min(object, nobjects - 1), so an INVALID record lies in the last
+ * object's segment; first[i] is the first slot of object i and first[nobjects] == npatches; slot k of an ADMITTED or
+ * DONE PATCH holds {data_offset, length}, every other slot {0, 0}.  Zero-length members are legal in every chain
+ * call and write nothing, so nextents == npatches is known on the host and no count has to come back before
+ * efes_objects_jobs is queued.  answers[a] (arrival order) holds the verdict, the answer's offset and the slot;
+ * patch_of[k] the arrival index of slot k; objects[i] = {cur, EFES_PATCH_OBJ_*, admitted PATCHes}; counts[v] the
+ * PATCHes with verdict v.  For a RESTARTED object sha1[i] becomes NewSha1() (x, nx, len and _pad zero) and
+ * crc32[i].crc 0; no other state is written.  With running sums (EFES_OBJECTS_RUNNING) the digests of a DONE PATCH
+ * are at sums + 24 * slot.
+ * Safety: every index that forms an address is clamped; whatever the log holds, first[] is non-decreasing from 0 to
+ * npatches and patch_of is a permutation; nothing outside the named outputs and the scratch is written.
+ * Errors, checked first and without the device: EFES_ERR_ARG for a NULL ctx (device call) or in; nobjects or
+ * npatches above EFES_OBJECTS_MAX; npatches > 0 with nobjects == 0; a NULL first, or with npatches > 0 a NULL log or
+ * extents; log, offsets, sha1, extents, answers or objects not 8-byte aligned; crc32, first, patch_of or counts not
+ * 4-byte aligned; and, on the device call, a scratch that is NULL, not 16-byte aligned or smaller than
+ * efes_patches_table_scratch(nobjects, npatches).  A refused call writes nothing.  With npatches == 0 the call
+ * writes first (all zeros), objects and counts and launches nothing else.
+ * The device call is asynchronous on `stream` (NULL = the context stream): no host read-back, allocation or wait.
+ * A stable LSD radix-256 sort of (key, arrival index), one digit pass up to 256 objects, two up to 65 536, three
+ * beyond, fixed on the host; first[] by a lower bound per object in the sorted keys; then the admission pass, the
+ * one serial dependency: an object of at most 64 PATCHes is walked by one lane, a longer one by a whole wavefront
+ * that loads 64 records at a time and resolves them run by run with ballots.  counts start at {npatches, 0, 0, 0, 0}
+ * and only a workgroup that holds another verdict than ADMITTED moves its numbers over with vector atomics
+ * (DESIGN.md §4 "PATCH logs").
+ * The _host twin is the same function over HOST arrays, with no context, stream or scratch.
+ * EFES_ABI_VERSION stays 8; a binding detects the calls by their symbols.
+ * Which path when (measured, profiles/patches/bench.json, tools/bench_patches.py; DESIGN.md §4 "PATCH logs" has the
+ * table; interleaved well-formed logs of 1 KiB bodies, and the same with 1 % conflicts, which change nothing below;
+ * wall-clock, nine repetitions, a path wins where its median is below the other's minimum; "device path" = the log
+ * (40 bytes per PATCH) and the offsets from host memory to the device, the call, a synchronise; "host path" = the
+ * host twin, then extents, first and the reset states to the device, a synchronise):
+ *   - 65 536 x 4, 262 144 x 4, 4096 x 64 and 1 048 576 x 1 uploads x PATCHes: the DEVICE path, at 0.14, 0.063, 0.35
+ *     and 0.037 of the host path's time -- 0.37 ms against 2.8, 1.07 against 17.8, 0.35 against 1.04 and 1.25 ms
+ *     against 34.5;
+ *   - ONE upload owning all 1 048 576 PATCHes: the HOST path, 3.7 ms against 17.4: the wavefront's 16 384 dependent
+ *     steps take about 1 us each.  A caller with one enormous upload in its log uses the twin;
+ *   - the call alone, device time: 62, 165, 130 and 221 us on the four shapes (16.6 ms on the degenerate one), three
+ *     to five times efes_objects_jobs behind it (22 to 44 us) and 0.1 to 0.4 of the wide walk (158 to 1727 us);
+ *   - the zero-length slots are NOT free in the walk: over a table with 10 % refused PATCHes efes_hash_chain_wide
+ *     takes 1.91, 1.73, 1.42 and 1.68 times what it takes over the same table compacted on the host (300 us against
+ *     157, 814 against 471, 2253 against 1586, 923 against 550).  Compacting needs a count back from the device in
+ *     front of the builder; a caller whose logs are full of refusals may prefer that. */
+#define EFES_PATCH_LENGTH_UNKNOWN (~(uint64_t)0) /* no efes-file-length header: Go's -1 */
+
+typedef struct efes_patch {        /* one PATCH request; the log is in ARRIVAL order */
+    uint64_t data_offset;          /* its body lies at data + data_offset */
+    uint64_t length;               /* body bytes: n of io.Copy (filereceiver.go:209) */
+    uint64_t file_offset;          /* efes-file-offset */
+    uint64_t file_length;          /* efes-file-length, or EFES_PATCH_LENGTH_UNKNOWN */
+    uint32_t object;               /* upload index, < nobjects */
+    uint32_t _reserved;
+} efes_patch;                      /* 40 bytes */
+
+typedef struct efes_patch_answer { /* per PATCH, arrival order */
+    uint64_t offset;               /* the efes-file-offset header of the answer */
+    uint32_t verdict;              /* EFES_PATCH_* */
+    uint32_t slot;                 /* the extent slot this PATCH has in the table */
+} efes_patch_answer;               /* 16 bytes */
+
+typedef struct efes_patch_object { /* per object */
+    uint64_t offset;               /* FileInfo.Offset after the log */
+    uint32_t flags;                /* EFES_PATCH_OBJ_* */
+    uint32_t admitted;             /* PATCHes of it that were admitted */
+} efes_patch_object;               /* 16 bytes */
+
+typedef struct efes_patches {      /* a HOST struct of device addresses (host addresses for the twin) */
+    const efes_patch* log;             /* npatches */
+    const uint64_t*   offsets;         /* nobjects: FileInfo.Offset before the log; NULL = all 0 */
+    efes_sha1_state*  sha1;            /* nobjects or NULL: states of RESTARTED objects are re-initialised */
+    efes_crc32_state* crc32;           /* nobjects or NULL: likewise */
+    efes_extent*      extents;         /* out, npatches */
+    uint32_t*         first;           /* out, nobjects + 1 */
+    efes_patch_answer* answers;        /* out, npatches, or NULL */
+    efes_patch_object* objects;        /* out, nobjects, or NULL */
+    uint32_t*         patch_of;        /* out, npatches, or NULL: slot -> arrival index */
+    uint32_t*         counts;          /* out, 5 words, or NULL: PATCHes per verdict */
+    uint32_t nobjects, npatches;
+} efes_patches;                    /* 88 bytes */
+
+#define EFES_PATCH_ADMITTED 0u  /* hashed; answer.offset = the new offset; .info is saved */
+#define EFES_PATCH_CONFLICT 1u  /* 409; answer.offset = the required offset */
+#define EFES_PATCH_DEFERRED 2u  /* not decided in this log: resubmit it in the next, in the same order */
+#define EFES_PATCH_DONE     3u  /* admitted and Offset == file_length: digests at sums + 24 * slot, .info goes */
+#define EFES_PATCH_INVALID  4u  /* object >= nobjects */
+
+#define EFES_PATCH_OBJ_RESTARTED 0x1u /* a PATCH at offset 0 was admitted: the states were re-initialised */
+#define EFES_PATCH_OBJ_DONE      0x2u /* a PATCH of it was DONE */
+#define EFES_PATCH_OBJ_DEFERRED  0x4u /* a PATCH of it was deferred */
+
+size_t efes_patches_table_scratch(uint32_t nobjects, uint32_t npatches);
+int efes_patches_table(efes_ctx* ctx, const efes_patches* in, void* scratch_device, size_t scratch_bytes, void* stream);
+int efes_patches_table_host(const efes_patches* in);
+
 /* Test hooks are declared in efes_testing.h: exported, but not part of the stable surface. */
 
 /* Pure text codecs on plain states (no device work). */
